@@ -1,6 +1,12 @@
 """bench.py - throughput of the MapCMA hot path on MI355X (driver contract: see DESIGN.md section 6).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: set-up, W warm-up steps, EXACTLY K timed steps, the JSON line.  Everything
+else listed below (the other rollout leg, roofline figures, CPU baselines, the DAgger legs, five repetitions) runs
+with --full.  --dump-outputs DIR writes what the headline's last timed step returned - actions, recurrent state,
+occupancy and semantic maps of rank 0 - as DIR/<name>.npy (float32, integers as float64; well under 1 MB); the
+inputs are seeded, so two builds can be compared output for output.
 
 With N > 1 and no WORLD_SIZE in the environment the parent spawns N ranks itself (one process per GPU through
 `python -m torch.distributed.run`, started BEFORE the parent touches the GPU) and relays rank 0's JSON line; when
@@ -10,9 +16,10 @@ A "step" = one pass of the hot path over one batch of synthetic observations alr
 Headline (`value`, `roofline`, `cpu_baseline`): BASELINE.json configs[2], the largest single-GPU configuration -
 RedNet-predicted semantics (rgb 224x224 + depth 256x256) -> egocentric mapper -> MapCMAPolicy.act for `--pred-envs`
 (default 8) parallel envs per GPU, env-steps/s over all ranks (weak scaling: envs per GPU fixed).  Every leg is timed
-as R = 5 repetitions of W warm-up + EXACTLY K steps, each bracketed by barrier + synchronize with the MAX over ranks
-taken per repetition; `value` / `ms_per_step` are the MEDIAN repetition and `repetitions` carries min / max.
-The JSON line also carries
+as W warm-up steps, then R repetitions (--reps: 1 in a plain run, 5 with --full) of EXACTLY K steps, each bracketed
+by barrier + synchronize with the MAX over ranks taken per repetition; `value` / `ms_per_step` are the MEDIAN
+repetition and `repetitions` carries min / max.
+With --full the JSON line also carries
   roofline             MFMA family of the headline step: achieved = algorithmic FLOPs of one step / the step's WALL time;
                        peak = the rate of the step's FLOP mix with the fp32 MFMA pipe (157.3 TF) and the bf16 MFMA pipe
                        (2.5 PF, six executed FLOPs per algorithmic FLOP of a split-bf16 conv) at their dense peaks;
@@ -353,7 +360,23 @@ def rollout_step(mapper_tr, policy, obs, state):
         actions, state["rnn"] = policy.act(batch, state["rnn"], state["prev"], batch["not_done_masks"],
                                            deterministic=True)
     state["prev"] = actions
+    state["maps"] = (batch.get("occupancy_map"), batch.get("semantic_map"))
     return actions
+
+
+def step_outputs(actions, rnn, maps):
+    """What a caller of the step receives, copied to the host: (B, 1) actions, (B, 2, 512) recurrent state and the
+    mapper's (B, 64, 64) occupancy / semantic maps."""
+    out = {"actions": actions, "rnn_states": rnn, "occupancy_map": maps[0], "semantic_map": maps[1]}
+    return {k: v.detach().cpu() for k, v in out.items() if v is not None}
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy per output: floating arrays as float32, integer ones (actions, u8 maps) as float64 - exact."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype.kind == "f" else np.float64))
 
 
 def usable_cores():
@@ -846,7 +869,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region per leg (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the other rollout leg, roofline figures, CPU baselines, the DAgger "
+                         "update / collection / iteration legs, 5 repetitions (a plain run times the headline's K steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the headline's outputs of its last timed step (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K-step timed region per leg (median reported; default 1, 5 with --full)")
     ap.add_argument("--envs", type=int, default=4, help="parallel envs per GPU of the gt-semantics leg (configs[1]: 4)")
     ap.add_argument("--pred-envs", type=int, default=8, help="envs per GPU of the pred-semantics headline (configs[2]: 8)")
     ap.add_argument("--pred-semantics", action="store_true", help="(default since round 4) configs[2] is the headline")
@@ -915,7 +944,7 @@ def main():
             return float(t.item())
         return seconds
 
-    K, W, R = args.steps, args.warmup, max(1, args.reps)
+    K, W, R = args.steps, args.warmup, max(1, args.reps if args.reps is not None else (5 if args.full else 1))
     cfg, policy = make_policy(dev)
 
     def rep_obj(ms_list, per="step"):
@@ -972,10 +1001,15 @@ def main():
                 i += 1
             barrier()
             ms.append(1e3 * max_over_ranks(time.perf_counter() - t0) / K)
+        outputs = None
+        if args.dump_outputs and pred == head_pred:
+            outputs = (step_outputs(runner.actions, runner.rnn_states, runner.maps()) if runner is not None
+                       else step_outputs(state["prev"], state["rnn"], state["maps"]))
         tr.mapping_module.check_status()
         del runner  # graphs hold the activation pools
         return {"ms": ms, "tr": tr, "obs_cpu": obs_cpu, "obs_dev": obs_dev, "state": state, "n_pool": n_pool, "B": B,
-                "launch": ("hipGraph replay, " + note) if note else "eager", "overlapped": note is not None and "2 streams" in note}
+                "launch": ("hipGraph replay, " + note) if note else "eager", "overlapped": note is not None and "2 streams" in note,
+                "outputs": outputs}
 
     def instrumented_mfma(leg, n_inst, what, traffic, busy=None):
         """MFMA-family figures of a leg from an eager pass with a start / stop event on every GEMM-family dispatch, the GPU
@@ -1007,7 +1041,7 @@ def main():
         obj = {"value": round(world * Bl / (med * 1e-3), 2), "unit": "env-steps/s", "ms_per_step": round(med, 4),
                "steps": K, "warmup": W, "repetitions": rep_obj(leg["ms"]), "envs_per_gpu": Bl,
                "config": {"workload": what_cfg, "envs_per_gpu": Bl, "launch": leg["launch"]}}
-        if rank == 0:
+        if rank == 0 and args.full:
             if pred:
                 obj["roofline"] = instrumented_mfma(leg, min(6, K), "RedNet + depth ResNet + map CNN launches of one step",
                                                     pmc_traffic_pair(f"predsem_B{Bl}_pmc_traffic.json"),
@@ -1028,7 +1062,7 @@ def main():
     W_GT = ("BASELINE configs[1]: MapCMA gt-semantics eval step = egocentric mapper + MapCMAPolicy.act, {B} parallel envs per "
             "GPU, 256x256 depth + semantic12, 80-token instruction, random-init weights of the reference architecture")
     head_pred = not args.gt_semantics
-    other = not (args.no_pred_leg or args.no_gt_leg)
+    other = args.full and not (args.no_pred_leg or args.no_gt_leg)
     legs = {}
     for pred in ((True, False) if head_pred else (False, True)):
         if pred != head_pred and not other:
@@ -1039,11 +1073,15 @@ def main():
         leg = run_leg(pred, Bl, K, W, seed=4321 if pred else 1234)
         log(f"rank {rank}: ms per step over {R} repetitions of {K} steps: " + ", ".join(f"{m:.4f}" for m in leg["ms"]))
         legs[pred] = leg_object(leg, pred, (W_PRED if pred else W_GT).format(B=Bl))
+        if leg["outputs"] is not None and rank == 0:
+            dump_outputs(leg["outputs"], args.dump_outputs)
+            log(f"outputs of the last timed step -> {args.dump_outputs}: " + ", ".join(
+                f"{k} {tuple(v.shape)}" for k, v in leg["outputs"].items()))
         del leg
 
     # ---- DAgger update step (fwd + bwd + all-reduce + Adam): reported beside the headline ----
     update = ul = None
-    if not args.no_update:
+    if args.full and not args.no_update:
         log(f"rank {rank}: update-step leg")
         ul = UpdateLeg(policy, dev, world)
         ums = ul.timed(barrier, max_over_ranks, iters=5, warm=2, reps=R)
@@ -1067,7 +1105,7 @@ def main():
 
     # ---- DAgger collection step (sampled action + beta-mix + host copies): the rollout half of configs[3] ----
     collect = iteration = None
-    if not args.no_collect:
+    if args.full and not args.no_collect:
         Bc, ck, cw = args.collect_envs, K, W
         log(f"rank {rank}: collection-step leg ({Bc} envs)")
         cl = CollectLeg(cfg, policy, dev, rank, B=Bc, graph=not args.no_graph)
@@ -1182,10 +1220,9 @@ if __name__ == "__main__":
     wd.cancel()
     sys.stdout.flush()
     sys.stderr.flush()
-    profiled = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-    if not profiled:
-        os._exit(0)  # the JSON line is out: skip interpreter / runtime teardown (graphs, streams) altogether
     import signal
 
+    # a normal exit, never os._exit: the exit handlers of whatever is loaded into the process (a profiler's finalizers,
+    # tools that record the native code a run used) must run; teardown gets two minutes, not forever
     signal.signal(signal.SIGALRM, signal.SIG_DFL)
-    signal.alarm(120)  # under a profiler its finalizers must run: give teardown two minutes, not forever
+    signal.alarm(120)

@@ -20,8 +20,32 @@ def _bench(args, env=None, timeout=900):
     return json.loads(lines[0])
 
 
+def test_plain_bench_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full the line is the headline alone - EXACTLY --steps timed steps, once - and --dump-outputs DIR holds what its
+    last timed step returned: actions, recurrent state and the two maps, integers exact as float64."""
+    import numpy as np
+
+    out = tmp_path / "outputs"
+    d = _bench(["--steps", "5", "--warmup", "2", "--dump-outputs", str(out)])
+    assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["repetitions"]["n"] == 1
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert "configs[2]" in d["config"]["workload"] and d["config"]["envs_per_gpu"] == 8
+    assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["roofline"] is None and "cpu_baseline" not in d
+    assert not {"gt_semantics_step", "update_step", "dagger_collect_step", "dagger_iteration"} & set(d)
+    a = {n: np.load(out / f"{n}.npy") for n in ("actions", "rnn_states", "occupancy_map", "semantic_map")}
+    assert sorted(p.name for p in out.iterdir()) == sorted(f"{n}.npy" for n in a)
+    assert a["actions"].shape == (8, 1) and a["actions"].dtype == np.float64 and set(np.unique(a["actions"])) <= {0, 1, 2, 3}
+    assert a["rnn_states"].shape == (8, 2, 512) and a["rnn_states"].dtype == np.float32 and np.isfinite(a["rnn_states"]).all()
+    assert np.abs(a["rnn_states"]).max() > 0
+    for n in ("occupancy_map", "semantic_map"):
+        assert a[n].shape == (8, 64, 64) and a[n].dtype == np.float64 and (a[n] == np.round(a[n])).all()
+        assert 0 <= a[n].min() and a[n].max() <= 255
+    assert a["occupancy_map"].max() > 0
+
+
 def test_bench_line_carries_the_contract_at_one_gpu():
-    d = _bench(["--steps", "4", "--warmup", "2", "--reps", "3", "--no-cpu-baseline"])
+    d = _bench(["--full", "--steps", "4", "--warmup", "2", "--reps", "3", "--no-cpu-baseline"])
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "env-steps/s"
     assert d["dtype"] == "f32" and "bf16" in d["dtype_note"]  # (the qualifier lives in dtype_note: ADVICE r5)
     assert d["ranks_seen"] == 1 and d["devices_seen"] == 1
@@ -104,8 +128,8 @@ def test_bench_line_carries_the_contract_at_one_gpu():
 
 
 def test_bench_gpus_2_on_one_device_reports_the_sum_over_ranks():
-    d = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--reps", "2", "--gt-semantics", "--no-pred-leg", "--no-update",
-                "--no-collect", "--no-cpu-baseline"], env={"IVLN_BENCH_ONE_DEVICE": "1"})
+    d = _bench(["--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--reps", "2", "--gt-semantics", "--no-pred-leg",
+                "--no-update", "--no-collect", "--no-cpu-baseline"], env={"IVLN_BENCH_ONE_DEVICE": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["envs_per_gpu"] == 4
     assert d["ranks_seen"] == 2 and d["devices_seen"] == 1 and d["collective_backend"] == "gloo"
     # whole-job value = envs of BOTH ranks per (max-over-ranks) step time
@@ -116,8 +140,8 @@ def test_bench_gpus_8_on_one_device_runs_the_update_collective_over_8_ranks():
     """configs[3]'s launch path at its real rank count: 8 ranks (all on cuda:0, gloo - control flow, not a
     measurement) each time the gt rollout leg and the DAgger update; the line reports the rank count the COLLECTIVE saw, the
     update's one all-reduce populated, and whole-job values = the sum over the 8 ranks."""
-    d = _bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--reps", "1", "--gt-semantics", "--no-pred-leg", "--no-collect",
-                "--no-cpu-baseline"], env={"IVLN_BENCH_ONE_DEVICE": "1"}, timeout=1500)
+    d = _bench(["--full", "--gpus", "8", "--steps", "3", "--warmup", "1", "--reps", "1", "--gt-semantics", "--no-pred-leg",
+                "--no-collect", "--no-cpu-baseline"], env={"IVLN_BENCH_ONE_DEVICE": "1"}, timeout=1500)
     assert d["n_gpus"] == 8 and d["ranks_seen"] == 8 and d["devices_seen"] == 1 and d["collective_backend"] == "gloo"
     assert abs(d["value"] - 8 * 4 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
     up = d["update_step"]

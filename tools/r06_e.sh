@@ -6,6 +6,6 @@ timeout 1500 python -m pytest tests -m gpu -x -q --timeout 300 > $O/pytest_gpu.t
 for i in 1 2 3; do timeout 600 python -m pytest tests/test_gpu_policy.py tests/test_gpu_predsem.py tests/test_gpu_rednet.py -x -q --timeout 120 2>&1 | tail -2; done
 P5="--no-update --no-collect --no-gt-leg --no-cpu-baseline --reps 3"
 for v in "IVLN_X=1" "IVLN_BF3_CONVT=0" "IVLN_PRED_DEPTH_START=layer4" "IVLN_PRED_DEPTH_START=layer4 IVLN_BF3_CONVT=0" "IVLN_PRED_DEPTH_START=layer3" "IVLN_X=1"; do
-  env $v timeout 300 python bench.py $P5 2>/dev/null | grep -o '"ms_per_step": [0-9.]*' | head -1 | sed "s/^/$v /"
+  env $v timeout 300 python bench.py --full $P5 2>/dev/null | grep -o '"ms_per_step": [0-9.]*' | head -1 | sed "s/^/$v /"
 done > $O/predsem_ab.txt 2>&1
 cat $O/predsem_ab.txt

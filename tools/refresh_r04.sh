@@ -20,13 +20,13 @@ timeout 200 tools/cluster_bench > $O/cluster_bench.txt 2>&1
 timeout 100 tools/graph_eager_repro > $O/graph_eager_repro.txt 2>&1
 timeout 200 python tools/depth_net_phases.py 4 > $O/depth_net_phases_N4.txt 2>&1
 timeout 100 python tools/depth_net_phases.py 8 2>&1 | grep "per launch\|sum of" > $O/depth_net_phases_N8.txt
-timeout 600 python bench.py > $O/bench_full.json 2> $O/bench_full.err
-timeout 300 python bench.py --gt-semantics --envs 8 --no-update --no-collect --no-pred-leg --no-cpu-baseline > $O/bench_gt_B8.json 2> $O/bench_gt_B8.err
+timeout 600 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
+timeout 300 python bench.py --full --gt-semantics --envs 8 --no-update --no-collect --no-pred-leg --no-cpu-baseline > $O/bench_gt_B8.json 2> $O/bench_gt_B8.err
 IVLN_REDNET_PLAN=0 timeout 200 python tools/gemm_shapes.py rednet > $O/rednet_B8_gemm_shapes.txt 2>&1
 # the split-bf16 conv against the fp32 MFMA kernels: time, error against float64, and where its workgroups spend their time
 timeout 300 python tools/conv_bf3_probe.py all > $O/conv_bf3_probe.txt 2>&1
 timeout 300 python tools/conv_bf3_phases.py > $O/conv_bf3_phases.txt 2>&1
-IVLN_SPLIT_BF16=0 timeout 300 python bench.py --no-cpu-baseline --no-collect --reps 3 > $O/bench_fp32_only.json 2> $O/bench_fp32_only.err
+IVLN_SPLIT_BF16=0 timeout 300 python bench.py --full --no-cpu-baseline --no-collect --reps 3 > $O/bench_fp32_only.json 2> $O/bench_fp32_only.err
 # where the split replay's time goes (end of each graph, per step), default build and the launch chain it replaced
 for B in 4 8; do
   for m in 1 0; do echo "== envs $B IVLN_DEPTH_NET=$m"; IVLN_DEPTH_NET=$m timeout 200 python tools/split_probe.py gt $B 2>&1 | tail -2; done
@@ -34,9 +34,9 @@ for B in 4 8; do
   echo "== envs $B IVLN_LSTM_SPARE=1 (no over-subscribed bi-LSTM grid)"; IVLN_LSTM_SPARE=1 timeout 200 python tools/split_probe.py gt $B 2>&1 | tail -2
 done > $O/split_probe.txt 2>&1
 # --- kernel traces ---
-run predsem --kernel-trace -d $O/predsem -- python3 bench.py --steps 50 --warmup 5 --reps 1 $PRED;               stats predsem predsem_B8_graph_kernel_stats.csv
-run graph   --kernel-trace -d $O/graph   -- python3 bench.py --steps 200 --warmup 20 --reps 1 $GT;               stats graph rollout_graph_kernel_stats.csv
-run eager   --kernel-trace -d $O/eager   -- python3 bench.py --steps 200 --warmup 20 --reps 1 $GT --no-graph;    stats eager rollout_eager_kernel_stats.csv
+run predsem --kernel-trace -d $O/predsem -- python3 bench.py --full --steps 50 --warmup 5 --reps 1 $PRED;               stats predsem predsem_B8_graph_kernel_stats.csv
+run graph   --kernel-trace -d $O/graph   -- python3 bench.py --full --steps 200 --warmup 20 --reps 1 $GT;               stats graph rollout_graph_kernel_stats.csv
+run eager   --kernel-trace -d $O/eager   -- python3 bench.py --full --steps 200 --warmup 20 --reps 1 $GT --no-graph;    stats eager rollout_eager_kernel_stats.csv
 run update  --kernel-trace -d $O/update  -- python3 bench.py --only-update --steps 5;                            stats update update_T64N8_kernel_stats.csv
 run rednet  --kernel-trace -d $O/rednet  -- python3 tools/bench_components.py rednet;                           stats rednet rednet_B8_kernel_stats.csv
 grep -h '"metric"' $O/predsem.log | tail -1 > $O/bench_predsem_B8.json
@@ -44,19 +44,19 @@ grep -h '"metric"' $O/graph.log | tail -1 > $O/bench_gt_graph.json
 # --- PMC passes: one counter per run, kernel trace only ---
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo $c | tr A-Z a-z)
-  run p_$n --kernel-trace --pmc $c -d $O/p_$n -- python3 bench.py --steps 10 --warmup 2 --reps 1 $PRED --no-graph;  pmc p_$n predsem_B8_pmc_$n.csv
-  run r_$n --kernel-trace --pmc $c -d $O/r_$n -- python3 bench.py --steps 20 --warmup 5 --reps 1 $GT --no-graph;    pmc r_$n rollout_pmc_$n.csv
+  run p_$n --kernel-trace --pmc $c -d $O/p_$n -- python3 bench.py --full --steps 10 --warmup 2 --reps 1 $PRED --no-graph;  pmc p_$n predsem_B8_pmc_$n.csv
+  run r_$n --kernel-trace --pmc $c -d $O/r_$n -- python3 bench.py --full --steps 20 --warmup 5 --reps 1 $GT --no-graph;    pmc r_$n rollout_pmc_$n.csv
   run u_$n --kernel-trace --pmc $c -d $O/u_$n -- python3 bench.py --only-update --steps 5;                          pmc u_$n update_pmc_$n.csv
 done
 # the launch chain the persistent depth encoder replaces, for the traffic A/B (IVLN_DEPTH_NET=0 is read by the library's python side)
 export IVLN_DEPTH_NET=0
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo $c | tr A-Z a-z)
-  run c_$n --kernel-trace --pmc $c -d $O/c_$n -- python3 bench.py --steps 20 --warmup 5 --reps 1 $GT --no-graph;    pmc c_$n rollout_chain_pmc_$n.csv
+  run c_$n --kernel-trace --pmc $c -d $O/c_$n -- python3 bench.py --full --steps 20 --warmup 5 --reps 1 $GT --no-graph;    pmc c_$n rollout_chain_pmc_$n.csv
 done
 unset IVLN_DEPTH_NET
-run pmfma --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d $O/p_mfma -- python3 bench.py --steps 10 --warmup 2 --reps 1 $PRED --no-graph; pmc p_mfma predsem_B8_pmc_mfma_util.csv
-run rmfma --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d $O/r_mfma -- python3 bench.py --steps 20 --warmup 5 --reps 1 $GT --no-graph;  pmc r_mfma rollout_pmc_mfma_util.csv
+run pmfma --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d $O/p_mfma -- python3 bench.py --full --steps 10 --warmup 2 --reps 1 $PRED --no-graph; pmc p_mfma predsem_B8_pmc_mfma_util.csv
+run rmfma --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d $O/r_mfma -- python3 bench.py --full --steps 20 --warmup 5 --reps 1 $GT --no-graph;  pmc r_mfma rollout_pmc_mfma_util.csv
 run umfma --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d $O/u_mfma -- python3 bench.py --only-update --steps 5;                         pmc u_mfma update_pmc_mfma_util.csv
 find $O -name "*.db" -delete
 # steps traced per pass: gt = warm-up 5 + timed 20 + instrumented roofline passes 20 + 20 (mapper) = 65; pred = 2 + 10 + 6 = 18; update = 2 + 5 + 1 = 8
