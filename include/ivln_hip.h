@@ -728,7 +728,9 @@ int ivln_attn_bwd_f32(const float* dout, int64_t ld_dout, const float* attn, con
                       int64_t dk_img_stride, float* dv, int64_t dv_img_stride, void* stream);
 /* the same with shared key/value images (ivln_attn_fwd_idx_f32): k / v are read through row_index, dk / dv are still
  * written per ROW; ivln_index_sum_f32 then folds them onto the images:
- *   dst[u][:] = sum_{r : index[r] == u} src[r][:]   (ascending r; M % 4 == 0, 16-byte aligned) */
+ *   dst[u][:] = sum_{r : index[r] == u} src[r][:]   (M % 4 == 0, 16-byte aligned)
+ * in a fixed order: the rows are cut into eight contiguous chunks of ceil(rows / 8), each chunk is summed in ascending r
+ * and the eight partial sums are added in chunk order - with rows <= 8 the plain ascending-r sum. */
 int ivln_attn_bwd_idx_f32(const float* dout, int64_t ld_dout, const float* attn, const float* q, int64_t ldq,
                           const float* k, int64_t k_img_stride, const float* v, int64_t v_img_stride, float scale,
                           int rows, int Ck, int Cv, int I, float* dq, int64_t ld_dq, float* dk,
@@ -767,6 +769,9 @@ int ivln_lstm_bidir_bwd_f32(const float* dout, const float* out, const float* ga
 int ivln_cbra_bwd_f32(const float* dout, const float* y, const float* scale, const float* shift,
                       const float* mean, const float* rstd, int N, int C, int H, int W, int train,
                       float* dgamma, float* dbeta, float* dy, float* ws, int64_t ws_floats, void* stream);
+/* embedding gradient: grad[tokens[r]][:] += d[r][:] onto the caller's (V, E) table gradient; tokens outside [0, V) and
+ * padding_idx (-1: none) are skipped.  The additions are float atomicAdd: their order is not fixed, so this is the one
+ * backward kernel whose result is NOT bit-stable from run to run (a token that fills many rows sums in any order). */
 int ivln_embedding_scatter_add_f32(const int64_t* tokens, const float* d, int rows, int E, int V,
                                    int padding_idx, float* grad, void* stream);
 int ivln_prev_action_embed_bwd_f32(const int64_t* prev_actions, const uint8_t* mask, const float* d1,

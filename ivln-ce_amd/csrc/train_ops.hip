@@ -578,6 +578,7 @@ __global__ __launch_bounds__(256) void k_cbra_bwd_stats(const float* __restrict_
             const float* dp = dout + ((int64_t)img * C + c) * Ho * Wo;
             for (int i = threadIdx.x * 4; i < HW; i += 1024) {
                 const int h = i / W, w = i - h * W;
+                if (h >= 2 * Ho) continue;  // odd H: the pool dropped the last row, dz = 0 there (W % 4 == 0 is even)
                 const float4 yv = *reinterpret_cast<const float4*>(yp + i);
                 const float2 dv = *reinterpret_cast<const float2*>(dp + (h >> 1) * Wo + (w >> 1));
                 const float d0 = fmaf(yv.x, sc, sh) > 0.f ? 0.25f * dv.x : 0.f;
@@ -599,7 +600,9 @@ __global__ __launch_bounds__(256) void k_cbra_bwd_stats(const float* __restrict_
             for (int i = threadIdx.x; i < HW; i += 256) {
                 int h = i / W, w = i - h * W;
                 float yv = yp[i];
-                float dz = fmaf(yv, sc, sh) > 0.f ? 0.25f * dp[(h >> 1) * Wo + (w >> 1)] : 0.f;
+                // odd H / W: AvgPool2d(2) floors, the last row / column reaches no output and has dz = 0
+                const bool pooled = h < 2 * Ho && w < 2 * Wo;
+                float dz = pooled && fmaf(yv, sc, sh) > 0.f ? 0.25f * dp[(h >> 1) * Wo + (w >> 1)] : 0.f;
                 s1 += (double)dz;
                 s2 += (double)(dz * ((yv - mu) * rs));
             }
@@ -649,7 +652,9 @@ __global__ __launch_bounds__(256) void k_cbra_bwd_apply4(const float* __restrict
     const int c = nc % C;
     const int h = i / W, w = i - h * W;
     const float4 yv = *reinterpret_cast<const float4*>(y + idx);
-    const float2 dv = *reinterpret_cast<const float2*>(dout + (int64_t)nc * Ho * Wo + (h >> 1) * Wo + (w >> 1));
+    // odd H: the last row was dropped by the pool (dz = 0); it still gets the train-mode mean terms below
+    const float2 dv = h < 2 * Ho ? *reinterpret_cast<const float2*>(dout + (int64_t)nc * Ho * Wo + (h >> 1) * Wo + (w >> 1))
+                                 : make_float2(0.f, 0.f);
     const float sc = scale[c], sh = shift[c];
     float yy[4] = {yv.x, yv.y, yv.z, yv.w};
     float dd[4] = {dv.x, dv.x, dv.y, dv.y};
@@ -687,7 +692,8 @@ __global__ __launch_bounds__(256) void k_cbra_bwd_apply(const float* __restrict_
     int h = i / W, w = i - h * W;
     float yv = y[idx];
     float sc = scale[c];
-    float dz = fmaf(yv, sc, shift[c]) > 0.f ? 0.25f * dout[(int64_t)nc * Ho * Wo + (h >> 1) * Wo + (w >> 1)] : 0.f;
+    const bool pooled = h < 2 * Ho && w < 2 * Wo;  // (odd H / W: see k_cbra_bwd_stats)
+    float dz = pooled && fmaf(yv, sc, shift[c]) > 0.f ? 0.25f * dout[(int64_t)nc * Ho * Wo + (h >> 1) * Wo + (w >> 1)] : 0.f;
     float v;
     if (train) {
         float M = (float)N * (float)HW;
@@ -765,13 +771,24 @@ __global__ __launch_bounds__(1024) void k_ce_iw_loss(const float* __restrict__ l
             for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
             float se = 0.f;
             for (int a = 0; a < A; ++a) se += expf(l[a] - mx);
-            float lse = mx + logf(se);
+            // log-softmax as (l - max) - log(sum): every term stays at the size of the logits' SPREAD.  Forming
+            // lse = max + log(sum) first rounds it at the size of the logits themselves - 8e-6 at |l| = 80 - and both the
+            // loss and exp(l - lse) inherit that (tests/test_gpu_train_kernels.py::test_ce_iw_loss: 50-1500x fp32 autograd).
+            float lsum = logf(se);
             int tg = (int)targets[t * N + n];
             float w = weights[t * N + n];
-            acc += w * (lse - l[tg]);
-            float coef = loss_scale * w / (wsum * (float)N);
-            for (int a = 0; a < A; ++a)
-                dlogits[((int64_t)t * N + n) * A + a] = coef * (expf(l[a] - lse) - (a == tg ? 1.f : 0.f));
+            acc += w * (lsum - (l[tg] - mx));
+            // softmax - onehot without the cancellation at the target: p_tg - 1 = -(sum of the other exps) / sum, so a
+            // saturated softmax (p_tg within an ulp of 1) keeps a gradient that is accurate relative to its own size
+            float coef = loss_scale * w / (wsum * (float)N) / se;
+            float others = 0.f;
+            for (int a = 0; a < A; ++a) {
+                if (a == tg) continue;
+                const float e = expf(l[a] - mx);
+                others += e;
+                dlogits[((int64_t)t * N + n) * A + a] = coef * e;
+            }
+            dlogits[((int64_t)t * N + n) * A + tg] = -coef * others;
         }
         acc = wave_sum(acc);
         total += acc / wsum;
@@ -842,16 +859,18 @@ __global__ __launch_bounds__(1024) void k_pm_masked_mean_fwd(const float* __rest
     float tot = 0.f, cnt = 0.f;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const float h = tanhf(pre[i]);
-        float sq = 0.f, d1 = 0.f;
+        // The two sums over j run in DOUBLE: a serial fp32 chain of n terms drifts by ~sqrt(n) roundings, and at n >= 10^4
+        // d(mean)/d(pre) was 13x further from a float64 run than torch's fp32 autograd is (tests/test_gpu_train_kernels.py).
+        double sq = 0.0, d1 = 0.0;
         for (int j = 0; j < n; ++j) {
             const float d = h - s_p[j];
-            sq = fmaf(d, d, sq);
-            d1 += d;
+            sq += (double)(d * d);
+            d1 += (double)d;
         }
         hat[i] = h;
-        dsum[i] = d1;
+        dsum[i] = (float)d1;
         if (mask[i]) {
-            tot += sq;
+            tot += (float)sq;
             cnt += (float)n;
         }
     }

@@ -1732,7 +1732,8 @@ def attn_bwd(dout, attn_p, q, k, v, scale, dq, dk, dv, row_index=None):
 
 
 def index_sum(src, index, U):
-    """dst[u] = sum of the rows of `src` (rows, ...) whose index is u, in ascending row order -> (U, ...)."""
+    """dst[u] = sum of the rows of `src` (rows, ...) whose index is u -> (U, ...), in a fixed order: eight contiguous row
+    chunks, each in ascending row order, added in chunk order (rows <= 8: the plain ascending sum)."""
     rows = src.shape[0]
     M = src[0].numel()
     dst = torch.empty((U,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)

@@ -134,13 +134,15 @@ def test_cbra_block(train):
 
     from ivln_ce_amd.encoders import CBRA
 
+    import copy
+
+    from ivln_ce_amd._lib import IvlnError
+
     torch.manual_seed(3)
     blk = CBRA(14, 32)
     blk.conv[1].running_mean.normal_(0, 0.1)
     blk.conv[1].running_var.uniform_(0.5, 1.5)
     blk.train(train)
-    import copy
-
     ref_blk = copy.deepcopy(blk)
     x = torch.randn(4, 14, 64, 64)
     ref = ref_blk.conv(x)
@@ -151,6 +153,13 @@ def test_cbra_block(train):
     if train:
         _close(blk.conv[1].running_mean, ref_blk.conv[1].running_mean, 1e-6)
         _close(blk.conv[1].running_var, ref_blk.conv[1].running_var, 1e-6)
+    # Odd sizes, (2, 6, 9, 11): AvgPool2d(2) would floor to 4 x 5, but the forward's pooling launcher reads pixel pairs
+    # and REFUSES odd H / W, loudly.  So the module never reaches the backward with an odd plane; only a caller of the
+    # C ABI can, and ivln_cbra_bwd_f32 handles it (tests/test_gpu_train_kernels.py::test_cbra_bwd).
+    odd = CBRA(6, 32).train(train).to(DEV)
+    with pytest.raises(IvlnError, match=r"ivln_scale_shift_relu_avgpool2_f32.*\(-1\)"):
+        with torch.no_grad():
+            odd.forward_hip(torch.randn(2, 6, 9, 11).to(DEV))
 
 
 def test_lstm_bidir_matches_packed_torch_lstm():

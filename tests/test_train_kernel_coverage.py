@@ -1,0 +1,92 @@
+"""CPU: every entry point of include/ivln_hip.h's backward / loss / optimizer section has a per-kernel GPU test of its own
+(tests/test_gpu_train_kernels.py::COVERED), and the index arithmetic of the BatchNorm -> ReLU -> AvgPool2d(2) backward
+restated in numpy, with and without the odd-size guard, against float64 autograd."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _backward_section_functions():
+    src = open(os.path.join(ROOT, "include", "ivln_hip.h")).read()
+    start = src.index("Backward / loss / optimizer kernels of the DAgger update")
+    end = src.index("ivln_dtw_symmetric1(")
+    assert 0 < start < end
+    sec = re.sub(r"/\*.*?\*/", "", src[src.rindex("/*", 0, start):end], flags=re.S)
+    return sorted(set(re.findall(r"\b(ivln_[a-z0-9_]+)\s*\(", sec)))
+
+
+def _uncovered(names, covered, module):
+    no_entry = [n for n in names if n not in covered]
+    no_test = [f"{n} -> {t}" for n, t in covered.items() if not callable(getattr(module, t, None)) or not t.startswith("test_")]
+    return no_entry, no_test
+
+
+def test_every_backward_entry_point_has_a_kernel_test():
+    import test_gpu_train_kernels as K
+
+    names = _backward_section_functions()
+    assert len(names) >= 24 and "ivln_cbra_bwd_f32" in names and "ivln_adam_step_guarded_f32" in names
+    assert "ivln_dtw_symmetric1" not in names and "ivln_cma_step_fwd" not in names
+    no_entry, no_test = _uncovered(names, K.COVERED, K)
+    assert not no_entry, f"declared in the header's backward section without a test in COVERED: {no_entry}"
+    assert not no_test, f"COVERED names tests that test_gpu_train_kernels.py does not define: {no_test}"
+    stale = [n for n in K.COVERED if n not in names]
+    assert not stale, f"COVERED lists functions the header's backward section does not declare: {stale}"
+    # the pin itself: one entry less, or a test that does not exist, is noticed
+    short = dict(K.COVERED)
+    short.pop("ivln_index_sum_f32")
+    assert _uncovered(names, short, K)[0] == ["ivln_index_sum_f32"]
+    assert _uncovered(names, dict(K.COVERED, ivln_add2d_f32="test_that_is_not_there"), K)[1]
+    # and the module's tests carry the gpu marker as a whole
+    assert K.pytestmark.name == "gpu"
+
+
+def _cbra_bwd_numpy(dout, y, gamma, beta, guard):
+    """train-mode ivln_cbra_bwd_f32 in float64 numpy with the kernel's index arithmetic: the pooled gradient of pixel (h, w)
+    is dout[(h >> 1) * Wo + (w >> 1)] of its plane; `guard` = pixels with h >= 2*Ho or w >= 2*Wo get dz = 0 instead.
+    Without it the flat index runs into the next pooled row, the next plane, or past the end (read as 0 here)."""
+    N, C, H, W = y.shape
+    Ho, Wo = H // 2, W // 2
+    mean, var = y.mean((0, 2, 3)), y.var((0, 2, 3))
+    rstd = 1.0 / np.sqrt(var + 1e-5)
+    xhat = (y - mean[None, :, None, None]) * rstd[None, :, None, None]
+    z = xhat * gamma[None, :, None, None] + beta[None, :, None, None]
+    flat = np.concatenate((dout.reshape(-1), np.zeros(Wo + 2)))
+    h, w = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    dz = np.zeros_like(y)
+    for n in range(N):
+        for c in range(C):
+            g = flat[(n * C + c) * Ho * Wo + (h >> 1) * Wo + (w >> 1)]
+            if guard:
+                g = np.where((h < 2 * Ho) & (w < 2 * Wo), g, 0.0)
+            dz[n, c] = np.where(z[n, c] > 0, 0.25 * g, 0.0)
+    M = N * H * W
+    s1, s2 = dz.sum((0, 2, 3)), (dz * xhat).sum((0, 2, 3))
+    dy = (gamma * rstd)[None, :, None, None] * (dz - s1[None, :, None, None] / M - xhat * s2[None, :, None, None] / M)
+    return dy, s2, s1
+
+
+@pytest.mark.parametrize("shape,odd", [((2, 3, 8, 8), False), ((2, 3, 6, 10), False), ((2, 3, 7, 8), True), ((2, 3, 8, 7), True),
+                                       ((2, 3, 25, 25), True)])
+def test_cbra_bwd_index_arithmetic_needs_the_odd_size_guard(shape, odd):
+    N, C, H, W = shape
+    g = torch.Generator().manual_seed(H * 100 + W)
+    y = torch.randn(N, C, H, W, generator=g, dtype=torch.float64)
+    gamma = torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    beta = torch.randn(C, generator=g, dtype=torch.float64) * 0.3
+    dout = torch.randn(N, C, H // 2, W // 2, generator=g, dtype=torch.float64)
+    yl, gl, bl = (t.clone().requires_grad_(True) for t in (y, gamma, beta))
+    F.avg_pool2d(F.relu(F.batch_norm(yl, None, None, gl, bl, training=True, eps=1e-5)), 2).backward(dout)
+    want = (yl.grad.numpy(), gl.grad.numpy(), bl.grad.numpy())
+    fixed = _cbra_bwd_numpy(dout.numpy(), y.numpy(), gamma.numpy(), beta.numpy(), guard=True)
+    old = _cbra_bwd_numpy(dout.numpy(), y.numpy(), gamma.numpy(), beta.numpy(), guard=False)
+    for a, b in zip(fixed, want):
+        assert np.abs(a - b).max() < 1e-12
+    old_err = max(np.abs(a - b).max() for a, b in zip(old, want))
+    assert (old_err > 1e-3) if odd else (old_err < 1e-12), old_err
