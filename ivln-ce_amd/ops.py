@@ -224,6 +224,21 @@ def gemm_soft(desc: GemmDesc) -> bool:
     return True
 
 
+def _gemm_observed(d: GemmDesc, splits, info):
+    """gemm() for the gradient wrappers' `splits` / `info` arguments (tests, tuning): `splits` forces ivln_gemm_desc.splits
+    (None: the wrapper's own choice, the descriptor unchanged); `info`, a dict, receives the split count the launch used as
+    info["splits_used"]."""
+    if splits is not None:
+        d.splits = int(splits)
+    if info is None:
+        gemm(d)
+        return
+    used = i32(0)
+    d.splits_used = C.pointer(used)
+    gemm(d)
+    info["splits_used"] = used.value
+
+
 _WORK_STREAMS = {}
 EAGER_WORK_STREAM = os.environ.get("IVLN_EAGER_WORK_STREAM", "1") != "0"
 
@@ -1892,7 +1907,7 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.9
 
 
 # ---- GEMM-shaped gradients ----------------------------------------------------------------------------
-def linear_bwd_input(dy, w, out=None, accumulate=False):
+def linear_bwd_input(dy, w, out=None, accumulate=False, splits=None, info=None):
     """dX[r][i] = sum_o dY[r][o] W[o][i]  (dy, out may be row-strided)."""
     rows, O = dy.shape
     I = w.shape[1]
@@ -1912,11 +1927,11 @@ def linear_bwd_input(dy, w, out=None, accumulate=False):
         d.ws, d.ws_floats, d.splits = dptr(ws), ws.numel(), 0
     else:
         d.splits = 1
-    gemm(d)
+    _gemm_observed(d, splits, info)
     return out
 
 
-def linear_bwd_weight(dy, x, out=None, accumulate=False):
+def linear_bwd_weight(dy, x, out=None, accumulate=False, splits=None, info=None):
     """dW[o][i] = sum_r dY[r][o] X[r][i]  -> (O, I) contiguous."""
     rows, O = dy.shape
     I = x.shape[1]
@@ -1935,14 +1950,14 @@ def linear_bwd_weight(dy, x, out=None, accumulate=False):
         d.ws, d.ws_floats, d.splits = dptr(ws), ws.numel(), 0
     else:
         d.splits = 1
-    gemm(d)
+    _gemm_observed(d, splits, info)
     return out
 
 
 WGRAD_EXACT_X = os.environ.get("IVLN_WGRAD_EXACT_X", "1") != "0"  # A/B: 0 = the one-hot first layer's weight gradient stages x as three pieces too
 
 
-def conv2d_bwd_weight(dy, x, KH, KW, stride=1, pad=0, x_exact_bf16=False):
+def conv2d_bwd_weight(dy, x, KH, KW, stride=1, pad=0, x_exact_bf16=False, splits=None, info=None):
     """dW (Cout, Cin, KH, KW) = sum over pixels dy[co][p] * im2col(x)[(ci,kh,kw)][p].
     x_exact_bf16: the caller's promise that every value of x is exact in bf16 (one-hot map features): the split-bf16 kernel
     stages x as one piece (ivln_gemm_desc.split_ok = 2; a broken promise gives NaNs, not a wrong gradient)."""
@@ -1963,5 +1978,5 @@ def conv2d_bwd_weight(dy, x, KH, KW, stride=1, pad=0, x_exact_bf16=False):
     ws = splitk_ws(dy.device)
     d.ws, d.ws_floats, d.splits = dptr(ws), ws.numel(), 0
     d.split_ok = int(SPLIT_BF16 and SPLIT_BF16_WGRAD) * (2 if (x_exact_bf16 and WGRAD_EXACT_X) else 1)
-    gemm(d)
+    _gemm_observed(d, splits, info)
     return out
