@@ -246,6 +246,17 @@ typedef struct ivln_gemm_desc {
      * (9 for a stride-2 3x3 transposed conv; 0 = all).  Arithmetic ignores it - the zero-padded taps multiply zeros - it only
      * makes ivln_conv_split_counters tally ALGORITHMIC FLOPs instead of executed ones. */
     int real_taps;
+    /* 1: a CBRA block of the map CNN as ONE launch (map_encoder.py:8-20: 7x7 conv, stride 1, pad 3 -> eval-mode BatchNorm
+     * -> ReLU -> AvgPool2d(2)).  The descriptor describes the conv (A_split its split-bf16 weights, Hout = Hin, Wout = Win,
+     * N = images * Hout * Wout); scale / shift = the BatchNorm folded with the conv bias, relu = 1; D is the POOLED
+     * (images, Ctot, Hout / 2, Wout / 2) tensor: D = avg2x2(relu(scale * conv + shift)), a window summed as
+     * (((a + b) + c) + d) * 0.25f.  Needs Hout % 4 == 0, Wout % 8 == 0, Cin <= 128; anything else: IVLN_E_UNSUPPORTED, and
+     * the caller issues the conv and ivln_scale_shift_relu_avgpool2_f32 (csrc/conv_bf3.hip: k_conv7_pool_bf3). */
+    int pool2;
+    /* with pool2, optional: the block's input is the map CNN's 14-channel feature tensor (occupancy ++ one_hot(label, 13),
+     * ivln_map_features_f32) which is never materialised - B = the u8 occupancy map (images, Hin, Win), map_sem_u8 = the u8
+     * label map of the same shape, Cin = 14. */
+    const uint8_t* map_sem_u8;
 } ivln_gemm_desc;
 
 int ivln_gemm_f32(const ivln_gemm_desc* desc, void* stream);

@@ -1026,6 +1026,256 @@ int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_p
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The map CNN's blocks at rollout batch (map_encoder.py:8-20: Conv 7x7 same -> BatchNorm (eval) -> ReLU -> AvgPool(2), 14 -> 32
+// -> 64 -> 128 -> 256 channels on 64x64 ... 8x8 maps of 1-16 images) as ONE launch each (ivln_gemm_desc.pool2).  The fp32 kernels
+// filled the chip there by splitting K over blockIdx.z: raw slabs to HBM, a reduction + pooling launch behind (16-64 slabs per
+// output in the tail layers).  Here, the scheme of k_conv_bf3_ks with a 7x7 window:
+//   * a workgroup of NW waves owns 32 output channels x a 4 x 8 pixel tile (whole 2x2 pooling windows: even origin, even
+//     extent) over the WHOLE K; wave w takes the 16-channel chunks w, w + NW, ... (NW = the chunk count, 1 ... 8: one chunk,
+//     49 taps, per wave at the CNN's shapes - 1024 waves per layer at 8 images);
+//   * wave-private patch (10 x 14 pixels x 112 bytes = 15.7 KB, 125 KB at NW = 8), wave-private weight stream a kernel row
+//     (7 taps) ahead, no barrier inside the K loop;
+//   * the partial tiles meet in LDS; a thread sums the four pixels of a pooling window over the waves in a fixed order,
+//     applies the folded scale / shift and the ReLU to each and stores (((a + b) + c) + d) * 0.25f - the order of
+//     k_scale_shift_relu_avgpool2 - into the pooled NCHW tensor.  No slabs, no second launch.
+//   * U8 (layer 1): the patch is built from the u8 occupancy and label maps themselves - channel 0 = the occupancy value,
+//     channel 1 + k = (label == k), labels >= 13 match nothing: what k_map_features4 writes - as ONE bf16 piece (every value
+//     is exact in bf16: the products against the lower pieces are exact zeros and are not issued), so the one-hot fp32
+//     tensor and its launch are gone.
+// ------------------------------------------------------------------------------------------------------------------
+template <int NW, bool U8>
+__global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_desc p, const unsigned char* a_split, int tiles_w, int tiles_h, int nimg) {
+    constexpr int KS = 7, KK = KS * KS, KKP = bf3_taps_padded(KS), DA = KS, PTH = 4, PTW = 8, NTB = 64 * NW;
+    constexpr int PH = PTH + KS - 1, PWR = PTW + KS - 1, NPIX = PH * PWR;
+    constexpr int XOFF = bf3_xoff(KS), NG = (XOFF + PWR + 3) / 4;
+    constexpr int ITEMS = PH * NG * (CB / 2), NI = U8 ? 1 : (ITEMS + 63) / 64;
+    constexpr int NPJ = (NPIX + 63) / 64;  // (U8: patch pixels per lane)
+    constexpr int WREG = (NPIX * PIXB + 15) & ~15;
+    constexpr int LDT = 32 + 4;
+    constexpr int NPL = U8 ? 1 : 3;  // pieces of the activations
+    constexpr unsigned OOB = 0x80000000u;
+    static_assert(KK % DA == 0, "the weight rotation closes over a chunk");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int half = lane >> 5, l31 = lane & 31;
+    const BlockId bid = xcd_block_id(p.no_xcd_remap);
+    const int bx = bid.x;
+    const int tw = bx % tiles_w, th = (bx / tiles_w) % tiles_h, img0 = bx / (tiles_w * tiles_h);
+    const int ho0 = th * PTH, wo0 = tw * PTW;
+    const int m0 = bid.y * 32;
+    const int nch = (p.Cin + CB - 1) / CB;
+    const int HW = p.Hin * p.Win;
+    const int niter = wave < nch ? (nch - wave + NW - 1) / NW : 0;  // chunks wave, wave + NW, ...
+    unsigned char* const wsm = smem + wave * WREG;
+
+    // f32 input: staging items of a lane = (patch row, aligned 16-byte group, channel pair), as in k_conv_bf3_ks
+    unsigned ivo[NI];
+    int idst[NI], imask[NI];
+    const int qpair = lane & 7;
+    if constexpr (!U8) {
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+            const int idx = lane + j * 64, rest = idx >> 3;
+            const int g = rest % NG, y = rest / NG;
+            const int hi = ho0 - KS / 2 + y, wi = wo0 - bf3_gx0(KS) + 4 * g;
+            const bool ok = idx < ITEMS && img0 < nimg && (unsigned)hi < (unsigned)p.Hin && wi >= 0 && wi + 3 < p.Win;
+            ivo[j] = ok ? (unsigned)(((int64_t)img0 * p.in_img_stride + (int64_t)(2 * qpair) * HW + hi * p.Win + wi) * 4) : OOB;
+            idst[j] = (y * PWR + 4 * g - XOFF) * PIXB + qpair * 4;
+            int m = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m |= (idx < ITEMS && (unsigned)(4 * g + e - XOFF) < (unsigned)PWR) ? (1 << e) : 0;
+            imask[j] = m;
+        }
+    }
+    const __amdgpu_buffer_rsrc_t rB = bf3_rsrc(p.B);
+    const unsigned hw4 = (unsigned)HW * 4u;
+    v4i rv[NI][2];
+    auto load_patch = [&](int c) {
+        if constexpr (!U8) {
+            const int so = c * CB * HW * 4;
+            const int left = p.Cin - c * CB;  // (a ragged last chunk - 14 channels - reads its missing channels as zero)
+            const bool ok0 = 2 * qpair < left, ok1 = 2 * qpair + 1 < left;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const bool in = !(ivo[j] & OOB);
+                rv[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)(in && ok0 ? ivo[j] : OOB), so, 0);
+                rv[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)(in && ok1 ? ivo[j] + hw4 : OOB), so, 0);
+            }
+        }
+    };
+    auto stage = [&]() {
+        if constexpr (!U8) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    uint32_t H, M, L;
+                    split3_pair(__int_as_float(rv[j][0][e]), __int_as_float(rv[j][1][e]), H, M, L);
+                    if ((imask[j] >> e) & 1) {
+                        unsigned char* d = wsm + idst[j] + e * PIXB;
+                        *reinterpret_cast<uint32_t*>(d) = H;
+                        *reinterpret_cast<uint32_t*>(d + 32) = M;
+                        *reinterpret_cast<uint32_t*>(d + 64) = L;
+                    }
+                }
+        } else {
+            // a patch pixel per lane and round: its two bytes -> the 16-channel record of the first piece (32 bytes: word q =
+            // channels 2 q, 2 q + 1).  Outside the image (the conv's zero padding): zeros, no label matches.
+            const uint8_t* const occ = reinterpret_cast<const uint8_t*>(p.B);
+            const uint8_t* const sem = p.map_sem_u8;
+            int ov[NPJ], sv[NPJ];
+#pragma unroll
+            for (int j = 0; j < NPJ; ++j) {
+                const int pix = lane + j * 64, y = pix / PWR, x = pix - y * PWR;
+                const int hi = ho0 - KS / 2 + y, wi = wo0 - KS / 2 + x;
+                const bool ok = pix < NPIX && img0 < nimg && (unsigned)hi < (unsigned)p.Hin && (unsigned)wi < (unsigned)p.Win;
+                const int64_t o = (int64_t)img0 * HW + hi * p.Win + wi;
+                ov[j] = ok ? (int)occ[o] : 0;
+                sv[j] = ok ? (int)sem[o] : -1;
+            }
+#pragma unroll
+            for (int j = 0; j < NPJ; ++j) {
+                const int pix = lane + j * 64;
+                constexpr uint32_t ONE = 0x3F80u;  // bf16 1.0
+                v4i w0, w1;
+                w0[0] = (int)((__float_as_uint((float)ov[j]) >> 16) | (sv[j] == 0 ? ONE << 16 : 0u));  // (0 ... 255: exact in bf16's 8 bits)
+#pragma unroll
+                for (int q = 1; q < 4; ++q) w0[q] = (int)((sv[j] == 2 * q - 1 ? ONE : 0u) | (sv[j] == 2 * q ? ONE << 16 : 0u));
+#pragma unroll
+                for (int q = 4; q < 7; ++q) w1[q - 4] = (int)((sv[j] == 2 * q - 1 ? ONE : 0u) | (sv[j] == 2 * q ? ONE << 16 : 0u));
+                w1[3] = 0;  // channels 14, 15: past Cin
+                if (pix < NPIX) {
+                    *reinterpret_cast<v4i*>(wsm + pix * PIXB) = w0;
+                    *reinterpret_cast<v4i*>(wsm + pix * PIXB + 16) = w1;
+                }
+            }
+        }
+    };
+    const int bbase = ((l31 / PTW) * PWR + (l31 % PTW)) * PIXB + half * 16;
+    const int mt = min(m0 / 32, (p.M + 31) / 32 - 1);
+    const __amdgpu_buffer_rsrc_t rA = bf3_rsrc(a_split + (int64_t)mt * nch * KKP * (3 * 1024));
+    const int q_last = max(niter * KK - 1, 0);
+    auto load_a = [&](int q, int pl) -> v4i {  // q: tap index in THIS wave's sequence (iteration i = q / 49 is chunk wave + i NW)
+        const int qc = min(q, q_last), i = qc / KK, r = qc - i * KK;
+        return __builtin_amdgcn_raw_buffer_load_b128(rA, (((wave + i * NW) * KKP + r) * 3 + pl) * 1024 + lane * 16, 0, 0);
+    };
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+
+    if (niter > 0) {
+        v4i abuf[DA][3];
+#pragma unroll
+        for (int d = 0; d < DA; ++d)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) abuf[d][pl] = load_a(d, pl);
+        load_patch(wave);
+        for (int i = 0; i < niter; ++i) {
+            stage();
+            const int s0 = i * KK;
+            auto read_b = [&](int r, bf16x8 (&b)[3]) {
+                const int kh = r / KS, kw = r - kh * KS, toff = (kh * PWR + kw) * PIXB;
+#pragma unroll
+                for (int pl = 0; pl < NPL; ++pl) b[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const v4i*>(wsm + bbase + toff + pl * 32));
+            };
+            bf16x8 bq[2][3];
+            read_b(0, bq[0]);
+#pragma unroll
+            for (int r = 0; r < KK; ++r) {
+                const int slot = r % DA;
+                if (r + 1 < KK) read_b(r + 1, bq[(r + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                bf16x8 a[3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) a[pl] = __builtin_bit_cast(bf16x8, abuf[slot][pl]);
+#define IVLN_BF3_PROD(PA, PB) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], bq[r & 1][PB], acc, 0, 0, 0)
+                if constexpr (!U8) {
+                    IVLN_BF3_PROD(0, 2);
+                    IVLN_BF3_PROD(1, 1);
+                }
+                IVLN_BF3_PROD(2, 0);
+                if constexpr (!U8) IVLN_BF3_PROD(0, 1);
+                IVLN_BF3_PROD(1, 0);
+                IVLN_BF3_PROD(0, 0);
+#undef IVLN_BF3_PROD
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) abuf[slot][pl] = load_a(s0 + r + DA, pl);
+                if (r == 1) load_patch(wave + min(i + 1, niter - 1) * NW);  // (the next chunk's patch: 47 taps of MFMA work before the staging pass reads it)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    // ---- the partial tiles meet in LDS: red[wave][32 channels][32 pixels (+4)] over the patch regions; then the CBRA tail ----
+    __syncthreads();
+    float* const red = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + l31] = acc[r];
+    __syncthreads();
+    const int Hp = p.Hout >> 1, Wp = p.Wout >> 1;
+    for (int idx = t; idx < 32 * (PTH / 2) * (PTW / 2); idx += NTB) {
+        const int ml = idx >> 3, pp = idx & 7, py = pp >> 2, px = pp & 3;  // (PTH / 2) x (PTW / 2) = 2 x 4 windows per channel
+        const int m = m0 + ml;
+        float2 tt = make_float2(0.f, 0.f), uu = make_float2(0.f, 0.f);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {  // fixed order: the sum does not depend on the run
+            const float* rp = red + (w * 32 + ml) * LDT + (2 * py) * PTW + 2 * px;
+            const float2 t2 = *reinterpret_cast<const float2*>(rp), u2 = *reinterpret_cast<const float2*>(rp + PTW);
+            tt.x += t2.x, tt.y += t2.y, uu.x += u2.x, uu.y += u2.y;
+        }
+        if (m < p.M && img0 < nimg) {
+            const float sc = p.scale[m], sh = p.shift[m];
+            const float a = fmaxf(fmaf(tt.x, sc, sh), 0.f), b = fmaxf(fmaf(tt.y, sc, sh), 0.f);
+            const float c2 = fmaxf(fmaf(uu.x, sc, sh), 0.f), d = fmaxf(fmaf(uu.y, sc, sh), 0.f);
+            p.D[(((int64_t)img0 * p.Ctot + m) * Hp + (ho0 >> 1) + py) * Wp + (wo0 >> 1) + px] = (((a + b) + c2) + d) * 0.25f;
+        }
+    }
+}
+
+template <int NW, bool U8>
+int launch_conv7_pool(const ivln_gemm_desc& d, hipStream_t s, int nimg) {
+    constexpr int WREG = ((4 + 6) * (8 + 6) * PIXB + 15) & ~15, RED = 32 * 36 * 4;
+    constexpr size_t lds = (size_t)NW * (WREG > RED ? WREG : RED);
+    static_assert(lds <= 160 * 1024, "patch regions do not fit");
+    auto kern = k_conv7_pool_bf3<NW, U8>;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
+        attr_done = true;
+    }
+    const int tiles_w = d.Wout / 8, tiles_h = d.Hout / 4;
+    dim3 grid(tiles_w * tiles_h * nimg, (d.M + 31) / 32, 1);
+    IVLN_LAUNCH_FAMILY_NAMED("k_conv7_pool_bf3", kern, grid, dim3(64 * NW), lds, s, d, (const unsigned char*)d.A_split, tiles_w, tiles_h, nimg);
+    return IVLN_OK;
+}
+
+// ivln_gemm_desc.pool2: eligibility of the fused map-CNN block.  Anything else is IVLN_E_UNSUPPORTED - the caller issues conv + tail.
+int bf3_conv7_pool_launch(ivln_gemm_desc& d, hipStream_t s) {
+    if (d.bmode != BMODE_CONV_K7 || d.amode != AMODE_MK || d.dmode != DMODE_NCHW || d.dil != 1 || d.stride != 1 || d.pad != 3 ||
+        d.Hout != d.Hin || d.Wout != d.Win || d.K != d.Cin * 49 || d.HoWo != d.Hout * d.Wout || d.N % d.HoWo != 0)
+        return IVLN_E_UNSUPPORTED;
+    if ((d.Hout & 3) || (d.Wout & 7) || !d.scale || !d.shift || !d.relu || d.residual || d.accumulate || d.residual_after_relu || d.defer_epilogue ||
+        d.splits > 1 || d.stat_partials || d.img_run_flags || d.fuse_A_split || d.grp_imgs > 0 || d.Cin > 8 * CB)
+        return IVLN_E_UNSUPPORTED;
+    const int nimg = d.N / d.HoWo;
+    const int64_t tiles = (int64_t)nimg * (d.Hout / 4) * (d.Wout / 8);
+    if (tiles >= (int64_t)1 << 30) return IVLN_E_UNSUPPORTED;
+    d.splits = 1;
+    if (d.map_sem_u8) {  // B = the u8 occupancy map, map_sem_u8 = the u8 labels: 1 + 13 channels built while staging
+        if (d.Cin != 14 || (int64_t)nimg * d.HoWo >= (int64_t)1 << 31) return IVLN_E_UNSUPPORTED;
+        return launch_conv7_pool<1, true>(d, s, nimg);
+    }
+    if ((d.in_img_stride & 3) || (((uintptr_t)d.B) & 15) || (int64_t)nimg * d.in_img_stride * 4 >= (int64_t)1 << 31) return IVLN_E_UNSUPPORTED;
+    const int nch = (d.Cin + CB - 1) / CB;
+    if (nch == 1) return launch_conv7_pool<1, false>(d, s, nimg);
+    if (nch == 2) return launch_conv7_pool<2, false>(d, s, nimg);
+    if (nch <= 4) return launch_conv7_pool<4, false>(d, s, nimg);
+    return launch_conv7_pool<8, false>(d, s, nimg);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // 1x1 convs with a deep K (RedNet's bottleneck reductions 1024 -> 256, 2048 -> 512, its 2048-channel expansions and skip
 // convs: rednet.py:20-65, 244-248) on the same arithmetic, K split over the waves of a workgroup, NO LDS in the K loop:
 //   * a workgroup (8 waves) owns 32 output channels x 128 consecutive pixels over the whole K, wave w the chunks
@@ -2099,6 +2349,11 @@ extern "C" int ivln_conv_bf3_stamps(unsigned long long* host, int n) {
 int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     constexpr bool disabled = false;  // A/B switch
     if (!d.A_split || (disabled && !force)) return IVLN_E_UNSUPPORTED;
+    if (d.pool2) {  // a map-CNN block as one launch (k_conv7_pool_bf3): K split over the waves, the CBRA tail in the epilogue
+        const int rc = bf3_conv7_pool_launch(d, s);
+        if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[1];
+        return rc;
+    }
     const int KS = d.bmode == BMODE_CONV1X1 ? 1 : conv_ks(d.bmode);
     if ((KS != 1 && KS != 2 && KS != 3 && KS != 7) || d.amode != AMODE_MK || d.dil != 1) return IVLN_E_UNSUPPORTED;
     if (KS == 7 && d.stride == 2) {  // RedNet's stems: A_split is the image of ivln_conv_stem_split_weights_f32 (the caller's contract)

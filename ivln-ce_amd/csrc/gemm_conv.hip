@@ -439,7 +439,7 @@ namespace {
 // every kernel that launches through IVLN_LAUNCH_FAMILY: the definition of "the MFMA family" (ivln_family_kernel_names)
 const char* const kFamilyKernels[] = {"k_gemm",     "k_gemm_vec",    "k_conv_direct",    "k_wgrad_direct", "k_conv1x1_stream", "k_conv_bf3",
                                       "k_conv_bf3_ks", "k_conv1x1_bf3_ks", "k_conv7s2_bf3", "k_wgrad_bf3",    "k_gn_conv",        "k_nconv",
-                                      "k_depth_net"};
+                                      "k_depth_net",   "k_conv7_pool_bf3"};
 constexpr int kFamilyCount = (int)(sizeof(kFamilyKernels) / sizeof(kFamilyKernels[0]));
 std::vector<hipEvent_t> g_timing_events;
 std::vector<int> g_timing_kernel;  // per timed launch: index into kFamilyKernels, kFamilyCount = a name outside the list
@@ -557,6 +557,14 @@ extern "C" int ivln_gemm_f32(const ivln_gemm_desc* desc, void* stream) {
     // residual behind the ReLU: only the stride-1 1x1 split-bf16 kernels have that epilogue form
     if (d.residual_after_relu) {
         if (!d.A_split || !d.residual || d.defer_epilogue || d.dmode != DMODE_NCHW || d.fuse_A_split || d.accumulate) return IVLN_E_UNSUPPORTED;
+        const int rc = ivln_conv_bf3_launch(d, s, true);
+        if (rc != IVLN_OK) return rc;
+        if (d.splits_used) *d.splits_used = 1;
+        return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+    }
+    // a map-CNN block with its BatchNorm + ReLU + AvgPool(2) tail in the epilogue (pool2): only conv_bf3.hip runs it
+    if (d.pool2) {
+        if (!d.A_split || d.defer_epilogue || d.dmode != DMODE_NCHW || d.fuse_A_split || d.tile_override) return IVLN_E_UNSUPPORTED;
         const int rc = ivln_conv_bf3_launch(d, s, true);
         if (rc != IVLN_OK) return rc;
         if (d.splits_used) *d.splits_used = 1;

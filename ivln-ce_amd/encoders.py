@@ -82,6 +82,20 @@ class CBRA(nn.Module):
         return ops.scale_shift_relu_avgpool2(ops.conv2d(x, self.conv[0].weight, pad=3, defer=True), scale, shift)
 
 
+    def forward_fused(self, x, maps_u8=None):
+        """Rollout path, one launch per block (ops.conv7_bn_relu_pool): the conv reduces K inside its workgroups and applies
+        folded BN + ReLU + AvgPool in its epilogue; `maps_u8` = the first block's u8 (occupancy, labels) instead of `x`.
+        None: the library declined the shape - the caller takes `forward_infer`."""
+        conv = self.conv[0]
+        if conv.kernel_size != (7, 7) or conv.stride != (1, 1) or conv.padding != (3, 3) or conv.dilation != (1, 1) or conv.groups != 1:
+            return None
+        scale, shift = self._folded()
+        return ops.conv7_bn_relu_pool(x, conv.weight, scale, shift, maps_u8=maps_u8)
+
+
+MAP_CNN_FUSED = True  # A/B, tests: False = the rollout's map CNN as conv (raw split-K slabs) + reducing tail, two launches per block
+
+
 class SemanticMapEncoder(nn.Module):
     def __init__(self, observation_space, num_semantic_classes: int = 13, ch: int = 32, last_ch_mult: int = 8,
                  trainable: bool = True, from_pretrained: bool = False, checkpoint: Optional[str] = None):
@@ -116,12 +130,25 @@ class SemanticMapEncoder(nn.Module):
         for k in ["occupancy_map", "semantic_map"]:
             if k not in observations:
                 raise ValueError(f"Observation `{k}` is missing.")
-        x = self.generate_map_features(observations)
-        for blk in self.cnn:
-            if save is None and not blk.conv[1].training:
-                x = blk.forward_infer(x)
-            else:
-                x = blk.forward_hip(x, save)
+        x = None
+        for k, blk in enumerate(self.cnn):
+            infer = save is None and not blk.conv[1].training
+            y = None
+            if infer and MAP_CNN_FUSED:
+                if k == 0 and self._num_semantic_classes == 13:  # (the u8 maps themselves: no feature tensor)
+                    occ = observations["occupancy_map"].to(torch.uint8).contiguous()
+                    sem = observations["semantic_map"].to(torch.uint8).contiguous()
+                    if occ.dim() == 3 and sem.dim() == 3:
+                        y = blk.forward_fused(None, maps_u8=(occ, sem))
+                if y is None:
+                    if k == 0:
+                        x = self.generate_map_features(observations)
+                    y = blk.forward_fused(x)
+            if y is None:
+                if k == 0 and x is None:
+                    x = self.generate_map_features(observations)
+                y = blk.forward_infer(x) if infer else blk.forward_hip(x, save)
+            x = y
         return x
 
 

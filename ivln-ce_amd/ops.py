@@ -46,6 +46,7 @@ class GemmDesc(C.Structure):
         ("fuse_A_split", vp), ("fuse_a_grp_stride", i64), ("fuse_scale", vp), ("fuse_shift", vp), ("fuse_M", i32),
         ("residual_after_relu", i32),
         ("real_taps", i32),
+        ("pool2", i32), ("map_sem_u8", vp),
     ]
 
 
@@ -536,6 +537,50 @@ def conv2d(x, w, stride=1, pad=0, dil=1, scale=None, shift=None, residual=None, 
         return out
     gemm(d)
     return out
+
+
+def conv7_bn_relu_pool(x, w, scale, shift, maps_u8=None, out=None):
+    """A CBRA block of the map CNN at rollout batch as ONE launch (csrc/conv_bf3.hip: k_conv7_pool_bf3): 7x7 same-size conv on the
+    split-bf16 arithmetic, K reduced inside the workgroup, then the folded scale / shift, the ReLU and the 2x2 average in the
+    epilogue - the pooled (N, Cout, H/2, W/2) tensor is all that is written.  `maps_u8` = (occupancy, labels), u8 (N, H, W):
+    the first block builds its 14-channel input (what map_features writes) while staging, `x` is then None.
+    Returns None when the library declines the shape (IVLN_E_UNSUPPORTED): the caller issues conv2d(defer) + the pooling tail."""
+    Cout, Cin, KH, KW = w.shape
+    if KH != 7 or KW != 7 or not SPLIT_BF16 or not w.is_contiguous():
+        return None
+    if maps_u8 is not None:
+        occ, sem = maps_u8
+        if (Cin != 14 or occ.dtype != torch.uint8 or sem.dtype != torch.uint8 or occ.shape != sem.shape or occ.dim() != 3
+                or not occ.is_contiguous() or not sem.is_contiguous()):
+            return None
+        N, H, W = occ.shape
+        src = occ
+    else:
+        if x.dim() != 4 or x.shape[1] != Cin or not x.is_contiguous():
+            return None
+        N, _, H, W = x.shape
+        src = x
+    if H % 2 or W % 2:
+        return None
+    sp = packed_conv_weights(w, split=True)
+    if sp is None:
+        return None
+    if out is None:
+        out = torch.empty((N, Cout, H // 2, W // 2), dtype=torch.float32, device=src.device)
+    d = GemmDesc()
+    d.A, d.B, d.D = dptr(w), _p(src), _p(out)
+    d.M, d.N, d.K = Cout, N * H * W, Cin * 49
+    d.amode, d.bmode, d.dmode = A_MK, B_CONV_K7, D_NCHW
+    d.lda = d.K
+    d.Cin, d.Hin, d.Win, d.Hout, d.Wout = Cin, H, W, H, W
+    d.stride, d.pad, d.dil = 1, 3, 1
+    d.HoWo, d.Ctot = H * W, Cout
+    d.A_split, d.a_split_grp_stride = dptr(sp), sp.numel()
+    _epilogue(d, scale, shift, None, True)
+    d.splits, d.pool2 = 1, 1
+    if maps_u8 is not None:
+        d.map_sem_u8 = _p(maps_u8[1])
+    return out if gemm_soft(d) else None
 
 
 _ALL_ROWS = {}
