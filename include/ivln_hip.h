@@ -822,6 +822,51 @@ int ivln_adam_step_guarded_f32(float* params, float* grads, float* exp_avg, floa
 int ivln_dtw_symmetric1(const double* a, int n, const double* b, int m, int dim, const uint8_t* window,
                         double* distance_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Masked LSTM state encoder: MODEL.STATE_ENCODER.rnn_type LSTM (csrc/lstm_state.hip).
+ * The reference builds both recurrent state encoders of MapCMANet with rnn_type=model_config.STATE_ENCODER.rnn_type
+ * (models/map_cma_policy.py:183,229) and slices rnn_states by each encoder's num_recurrent_layers (:290-351); with LSTM
+ * that is habitat-lab's RNNStateEncoder over nn.LSTM(input, hidden, num_layers=1): gate order i, f, g, o; in the
+ * batch-first state (N, 2, H) slot 0 is h and slot 1 is c.  All fp32.  H % 4 == 0, else IVLN_E_INVALID.
+ *   h' = h * mask, c' = c * mask;  gates = W_ih x + b_ih + W_hh h' + b_hh
+ *   c_t = s(f) c' + s(i) tanh(g);  h_t = s(o) tanh(c_t)
+ * There is no single-launch (persistent) form and no fused-head form of this encoder: a sequence is one launch per
+ * timestep, and ivln_cma_step_fwd stays GRU arithmetic.
+ * ------------------------------------------------------------------------------------------ */
+/* One masked step (RNNStateEncoder single_forward, or one step of seq_forward) for `rows` states.  Input: x (rows, I)
+ * row stride ldx with w_ih (4H, I) / b_ih (4H), or gi_pre (rows, 4H) row stride ldgi = W_ih x + b_ih precomputed
+ * (exactly one of x / gi_pre).  h_in / c_in (rows, H) with row strides ldh / ldc (slices of the (N, L, H) state tensor);
+ * mask u8 (rows) or NULL; w_hh (4H, H), b_hh (4H) or NULL.  h_t -> h_out (row stride ldo) and, when given, h_out2 (row
+ * stride ldo2: the state tensor's h slot); c_t -> c_out (row stride ldco).  c_out may be c_in; h_out / h_out2 must not
+ * overlap h_in.  Optional saves for ivln_lstm_seq_bwd_f32, all five or none: the activated gates i, f, g, o and c_t,
+ * (rows, H) contiguous each.  16-byte loads when x / h_in / w_ih / w_hh and their row strides allow, else 4-byte loads. */
+int ivln_lstm_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, int64_t ldgi, const float* h_in,
+                       int64_t ldh, const float* c_in, int64_t ldc, const uint8_t* mask, const float* w_ih,
+                       const float* w_hh, const float* b_ih, const float* b_hh, float* h_out, int64_t ldo, float* h_out2,
+                       int64_t ldo2, float* c_out, int64_t ldco, int rows, int H, float* save_i, float* save_f,
+                       float* save_g, float* save_o, float* save_c, void* stream);
+/* The same step over a time-major (T*N rows) sequence batch in ONE call (RNNStateEncoder seq_forward; the forward of
+ * base_il_trainer.py:173-219): T dependent launches of the step kernel enqueued on `stream`.  gi (T*N, 4H) = W_ih x + b_ih
+ * for all rows (the caller's GEMM); h0 / c0 (N, H) row strides ld_h0 / ld_c0; masks u8 (T*N), applied at every step ->
+ * out (T*N, H) row stride ldo; the last step's h also to h_state_out (or NULL); c_state_out (N, H), REQUIRED, holds the
+ * cell state from step 0 on (advanced in place) and ends as the last step's c.  Saves as above with T*N rows. */
+int ivln_lstm_seq_fwd_f32(const float* gi, const float* h0, int64_t ld_h0, const float* c0, int64_t ld_c0,
+                          const uint8_t* masks, const float* w_hh, const float* b_hh, float* out, int64_t ldo,
+                          float* h_state_out, int64_t ld_hs, float* c_state_out, int64_t ld_cs, int T, int N, int H,
+                          float* save_i, float* save_f, float* save_g, float* save_o, float* save_c, void* stream);
+/* BPTT of ivln_lstm_seq_fwd_f32 (T = 1: of ivln_lstm_step_f32) in one call (torch autograd of the same loop), in reverse
+ * time order: the element part of step T-1, T-1 launches that carry step t into step t-1 and run its element part, and
+ * one that carries step 0 into the initial state.  d_out (T*N, H) row stride ld_dout; the forward's five saves, its `out`
+ * (row stride ld_out), h0 / c0 and masks; whh_t = W_hh^T (H, 4H).  Writes dgi (T*N, 4H), the gradient of the gate
+ * pre-activations (of gi AND of W_hh h' + b_hh: they are one sum); hp (T*N, H) = h_{t-1} * mask_t, the rows
+ * dW_hh = dgi^T . hp needs; dh0 / dc0 (N, H) row strides ld_dh0 / ld_dc0.  A step whose mask is 0 sends exactly zero into
+ * the previous state.  dc0 doubles as the chain's running dc_t * f_t between launches.  whh_t and dgi 16-byte aligned. */
+int ivln_lstm_seq_bwd_f32(const float* d_out, int64_t ld_dout, const float* save_i, const float* save_f,
+                          const float* save_g, const float* save_o, const float* save_c, const float* out, int64_t ld_out,
+                          const float* h0, int64_t ld_h0, const float* c0, int64_t ld_c0, const uint8_t* masks,
+                          const float* whh_t, int T, int N, int H, float* dgi, float* hp, float* dh0, int64_t ld_dh0,
+                          float* dc0, int64_t ld_dc0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ SOURCES = {
     "depth_net.hip": [],
     "cma_step.hip": [],
     "gru_seq.hip": [],
+    "lstm_state.hip": [],
     "nn_ops.hip": [],
     "train_ops.hip": [],
     "dtw.cpp": [],

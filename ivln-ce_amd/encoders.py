@@ -584,7 +584,7 @@ class VlnResnetDepthEncoder(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-# RNN state encoder (masked GRU)
+# RNN state encoders (masked GRU; masked LSTM)
 # ------------------------------------------------------------------------------------------------
 class RNNStateEncoder(nn.Module):
     def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1):
@@ -623,6 +623,48 @@ class RNNStateEncoder(nn.Module):
         return out
 
 
+class LSTMStateEncoder(nn.Module):
+    """STATE_ENCODER.rnn_type LSTM: habitat-lab's RNNStateEncoder over nn.LSTM (the reference passes the key through,
+    map_cma_policy.py:183,229).  Two recurrent "layers" in the batch-first state: slot 0 is h, slot 1 is c."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1):
+        super().__init__()
+        assert num_layers == 1
+        self.num_recurrent_layers = 2 * num_layers
+        self.rnn = nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
+        for name, param in self.rnn.named_parameters():
+            if "weight" in name:
+                nn.init.orthogonal_(param)
+            elif "bias" in name:
+                nn.init.constant_(param, 0)
+
+    def forward(self, x, state_in, masks_u8, out, state_out, save=None):
+        """The RNNStateEncoder.forward contract with (N,2,H) state views: x (rows,I); state_in / state_out (N,2,H)
+        row-strided slices [h | c] of the incoming / outgoing state; masks u8 (rows); `out` (rows,H) row-strided
+        destination of the per-step outputs.  rows == N -> single step, else time-major sequence of T = rows/N steps."""
+        rnn = self.rnn
+        rows, N = x.shape[0], state_in.shape[0]
+        H = rnn.hidden_size
+        h0, c0 = state_in[:, 0], state_in[:, 1]
+        T = rows // N
+        saves = None
+        if save is not None:
+            saves = tuple(torch.empty((rows, H), dtype=torch.float32, device=x.device) for _ in range(5))
+            save.update(saves=saves, T=T, N=N, x=x, h0=h0, c0=c0, masks=masks_u8, out=out)
+        if rows == N:
+            ops.lstm_step(x, None, h0, c0, masks_u8, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                          out, state_out[:, 1], state_out[:, 0], saves)
+            return out
+        gi = ops.linear_gemm(x, rnn.weight_ih_l0, rnn.bias_ih_l0)
+        ops.lstm_seq(gi, h0, c0, masks_u8, rnn.weight_hh_l0, rnn.bias_hh_l0, out, state_out[:, 0], state_out[:, 1], T, N,
+                     saves)
+        return out
+
+
 def build_rnn_state_encoder(input_size: int, hidden_size: int, rnn_type: str = "GRU", num_layers: int = 1):
-    assert rnn_type.lower() == "gru", "MapCMA configs use STATE_ENCODER.rnn_type GRU"
-    return RNNStateEncoder(input_size, hidden_size, num_layers)
+    kind = str(rnn_type).lower()
+    if kind == "gru":
+        return RNNStateEncoder(input_size, hidden_size, num_layers)
+    if kind == "lstm":
+        return LSTMStateEncoder(input_size, hidden_size, num_layers)
+    raise ValueError(f"MODEL.STATE_ENCODER.rnn_type must be GRU or LSTM, got {rnn_type!r}")

@@ -116,6 +116,10 @@ class LatentCMANet(Net):
     def __init__(self, observation_space, model_config, num_actions):
         super().__init__()
         self.model_config = model_config
+        if str(model_config.STATE_ENCODER.rnn_type).lower() != "gru":
+            # forward_hip / backward_hip below are GRU arithmetic; the LSTM state encoder is MapCMA-only so far
+            raise ValueError("LatentCMANet supports MODEL.STATE_ENCODER.rnn_type GRU only, got "
+                             f"{model_config.STATE_ENCODER.rnn_type!r}")
         model_config.defrost()
         model_config.INSTRUCTION_ENCODER.final_state_only = False
         model_config.freeze()

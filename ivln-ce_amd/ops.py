@@ -1455,6 +1455,56 @@ def gru_seq_bwd(d_out, r, z, n, ghn, out, h0, masks_u8, whh_t, T, N, dgi, dgh, h
                                  dptr(dhz), _p(_seq_ws(r.device)), stream_ptr()), "ivln_cma_seq_bwd_f32")
 
 
+def _ld(t):
+    return t.stride(0) if t is not None else 0
+
+
+def lstm_step(x, gi_pre, h_in, c_in, mask_u8, w_ih, w_hh, b_ih, b_hh, h_out, c_out, h_out2=None, saves=None):
+    """One masked LSTM step over `rows` rows (STATE_ENCODER.rnn_type LSTM); x (rows,I) or gi_pre (rows,4H); h_in / c_in /
+    h_out / h_out2 / c_out row-strided (rows,H) views; saves: (i, f, g, o, c) (rows,H) contiguous each, or None."""
+    rows = h_in.shape[0]
+    H = w_hh.shape[1]
+    s = saves or (None,) * 5
+    L = _L()
+    L.ivln_lstm_step_f32.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64,
+                                     i32, i32, vp, vp, vp, vp, vp, vp]
+    check(
+        L.ivln_lstm_step_f32(_p(x), _ld(x), w_ih.shape[1] if x is not None else 0, _p(gi_pre), _ld(gi_pre), _p(h_in),
+                             h_in.stride(0), _p(c_in), c_in.stride(0), _p(mask_u8), dptr(w_ih) if x is not None else None,
+                             dptr(w_hh), dptr(b_ih) if x is not None else None, dptr(b_hh), _p(h_out), h_out.stride(0),
+                             _p(h_out2), _ld(h_out2), _p(c_out), c_out.stride(0), rows, H, *[_p(t) for t in s],
+                             stream_ptr()),
+        "ivln_lstm_step_f32",
+    )
+
+
+def lstm_seq(gi, h0, c0, masks_u8, w_hh, b_hh, out, h_state_out, c_state_out, T, N, saves=None):
+    """Masked LSTM over T timesteps of N rows in one C-ABI call: T dependent launches of the step kernel enqueued from C
+    (there is no persistent form).  gi (T*N,4H) contiguous; out (T*N,H) row-strided; c_state_out (N,H) is required."""
+    H = w_hh.shape[1]
+    s = saves or (None,) * 5
+    L = _L()
+    L.ivln_lstm_seq_fwd_f32.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, vp,
+                                        vp, vp, vp, vp]
+    check(L.ivln_lstm_seq_fwd_f32(dptr(gi), _p(h0), h0.stride(0), _p(c0), c0.stride(0), dptr(masks_u8), dptr(w_hh),
+                                  dptr(b_hh), _p(out), out.stride(0), _p(h_state_out), _ld(h_state_out), _p(c_state_out),
+                                  c_state_out.stride(0), T, N, H, *[_p(t) for t in s], stream_ptr()),
+          "ivln_lstm_seq_fwd_f32")
+
+
+def lstm_seq_bwd(d_out, saves, out, h0, c0, masks_u8, whh_t, T, N, dgi, hp, dh0, dc0):
+    """BPTT of lstm_seq / lstm_step (T = 1): d_out (T*N,H) row-strided, saves = the forward's (i, f, g, o, c), whh_t =
+    W_hh^T (H,4H) -> dgi (T*N,4H), hp (T*N,H) = masked h_{t-1}, dh0 / dc0 (N,H) row-strided."""
+    H = whh_t.shape[0]
+    L = _L()
+    L.ivln_lstm_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, vp,
+                                        vp, vp, i64, vp, i64, vp]
+    check(L.ivln_lstm_seq_bwd_f32(_p(d_out), d_out.stride(0), *[dptr(t) for t in saves], _p(out), out.stride(0), _p(h0),
+                                  h0.stride(0), _p(c0), c0.stride(0), dptr(masks_u8), dptr(whh_t), T, N, H, dptr(dgi),
+                                  dptr(hp), _p(dh0), dh0.stride(0), _p(dc0), dc0.stride(0), stream_ptr()),
+          "ivln_lstm_seq_bwd_f32")
+
+
 def attn(q, k, v, valid_len, scale, out, save_attn=None, row_index=None):
     """q (rows,Ck) strided rows; k (imgs,Ck,I), v (imgs,Cv,I) with image strides; out (rows,Cv) strided.
     row_index (rows,) i32: the key/value image of each row (None: row r uses image r); valid_len is per image."""

@@ -16,7 +16,8 @@ from torch import Tensor
 
 from . import ops
 from .aux_losses import AuxLosses
-from .encoders import InstructionEncoder, SemanticMapEncoder, VlnResnetDepthEncoder, build_rnn_state_encoder
+from .encoders import (InstructionEncoder, RNNStateEncoder, SemanticMapEncoder, VlnResnetDepthEncoder,
+                       build_rnn_state_encoder)
 from .registry import baseline_registry
 
 try:  # pragma: no cover
@@ -69,7 +70,8 @@ class CategoricalNet(nn.Module):
 
 class MapCMANet(Net):
     """Cross-modal attention network: instruction bi-LSTM, DD-PPO depth ResNet, semantic-map CNN,
-    two GRU state encoders and three attentions (map_cma_policy.py:103-368)."""
+    two recurrent state encoders (GRU, or LSTM with STATE_ENCODER.rnn_type LSTM) and three attentions
+    (map_cma_policy.py:103-368)."""
 
     def __init__(self, observation_space, config, num_actions):
         super().__init__()
@@ -162,6 +164,17 @@ class MapCMANet(Net):
     def num_recurrent_layers(self):
         return self.state_encoder.num_recurrent_layers + self.second_state_encoder.num_recurrent_layers
 
+    @property
+    def _gru_encoders(self):
+        """Both state encoders are GRUs: what the fused recurrent head (ivln_cma_step_fwd, GRU arithmetic) requires."""
+        return isinstance(self.state_encoder, RNNStateEncoder) and isinstance(self.second_state_encoder, RNNStateEncoder)
+
+    @staticmethod
+    def _state_slot(states, first, n):
+        """The n recurrent layers from `first` on of a batch-first (N, L, H) state, as an encoder takes them: (N, H) for
+        the GRU's single layer, (N, n, H) otherwise (map_cma_policy.py:290-351 slices by num_recurrent_layers)."""
+        return states[:, first] if n == 1 else states[:, first:first + n]
+
     def _cma_fold_weights(self):
         """Instruction-side folds of the fused rollout head (csrc/cma_step.hip), cached until the weights change:
         rows 0..H-1 = W_q^T W_k, row H = b_q^T W_k (shift: the same rows applied to b_k), then W_tq / b_tq - one
@@ -184,7 +197,7 @@ class MapCMANet(Net):
     def prepare_capture(self, example_obs):
         """Create everything the rollout step caches lazily BEFORE a stream capture (graphed.py): a buffer born inside
         a capture lives in that graph's private pool and must not survive in a process-wide cache."""
-        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs:
+        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or not self._gru_encoders:
             return
         rows, L = example_obs["instruction"].shape[0], example_obs["instruction"].shape[1]
         P = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
@@ -201,7 +214,7 @@ class MapCMANet(Net):
     # ------------------------------------------------------------------------------------------
     def forward_hip(self, observations, rnn_states, prev_actions, action_masks, save=None):
         """HIP forward of map_cma_policy.py:276-353.  Returns (features (rows,512), rnn_states_out
-        (N,2,512)).  `save` (dict) collects what the HIP backward needs."""
+        (N, num_recurrent_layers, H)).  `save` (dict) collects what the HIP backward needs."""
         mc = self.model_config
         dev = rnn_states.device
         H = self._hidden_size
@@ -234,7 +247,7 @@ class MapCMANet(Net):
         # outside the kernel's envelope takes the unfused chain with a real text_k.
         P_static = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         L_static = observations["instruction"].shape[-1] if "instruction" in observations else 0
-        fused_head = (save is None and ops.CMA_STEP_MODE >= 0
+        fused_head = (save is None and ops.CMA_STEP_MODE >= 0 and self._gru_encoders
                       and not (mc.ablate_instruction or mc.ablate_depth or mc.ablate_map)
                       and P_static <= 16 and 0 < L_static <= 512
                       and self.map_encoder.output_shape[1] * self.map_encoder.output_shape[2] == P_static
@@ -420,7 +433,9 @@ class MapCMANet(Net):
         s_g1 = {} if save is not None else None
         s_g2 = {} if save is not None else None
         state = x2[:, :H]
-        self.state_encoder(state_in, rnn_states[:, 0], masks_u8, state, rnn_out[:, 0], s_g1)
+        n1, n2 = self.state_encoder.num_recurrent_layers, self.second_state_encoder.num_recurrent_layers
+        self.state_encoder(state_in, self._state_slot(rnn_states, 0, n1), masks_u8, state,
+                           self._state_slot(rnn_out, 0, n1), s_g1)
 
         q1 = ops.linear(state, self.state_q.weight, self.state_q.bias)
         a_txt = torch.empty((rows, L), dtype=torch.float32, device=dev) if save is not None else None
@@ -442,7 +457,8 @@ class MapCMANet(Net):
         sc = self.second_state_compress[0]
         c2 = ops.linear(x2, sc.weight, sc.bias, relu=True)
         feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
-        self.second_state_encoder(c2, rnn_states[:, 1], masks_u8, feats, rnn_out[:, 1], s_g2)
+        self.second_state_encoder(c2, self._state_slot(rnn_states, n1, n2), masks_u8, feats,
+                                  self._state_slot(rnn_out, n1, n2), s_g2)
 
         if save is not None:
             save.update(

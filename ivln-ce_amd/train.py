@@ -154,6 +154,32 @@ def _gru_backward(enc, s, d_out, G):
     return ops.linear_bwd_input(dgi, rnn.weight_ih_l0)
 
 
+def _lstm_backward(enc, s, d_out, G):
+    """BPTT of the masked LSTM state encoder (STATE_ENCODER.rnn_type LSTM); returns d(x) (rows, I).  The gate
+    pre-activations are ONE sum of the input and the recurrent half, so one dgi serves both weight gradients and both
+    biases; the initial state takes no gradient here (dh0 / dc0 are written and dropped)."""
+    rnn = enc.rnn
+    T, N = s["T"], s["N"]
+    H = rnn.hidden_size
+    rows = T * N
+    dev = d_out.device
+    whh_t = ops.transpose(rnn.weight_hh_l0)  # (H, 4H)
+    dgi = torch.empty((rows, 4 * H), dtype=torch.float32, device=dev)
+    hp = torch.empty((rows, H), dtype=torch.float32, device=dev)
+    d0 = torch.empty((N, 2, H), dtype=torch.float32, device=dev)
+    ops.lstm_seq_bwd(d_out, s["saves"], s["out"], s["h0"], s["c0"], s["masks"], whh_t, T, N, dgi, hp, d0[:, 0], d0[:, 1])
+    G[rnn.weight_ih_l0] = ops.linear_bwd_weight(dgi, s["x"])
+    G[rnn.weight_hh_l0] = ops.linear_bwd_weight(dgi, hp)
+    G[rnn.bias_ih_l0] = G[rnn.bias_hh_l0] = _colsum(dgi)
+    return ops.linear_bwd_input(dgi, rnn.weight_ih_l0)
+
+
+def _state_encoder_backward(enc, s, d_out, G):
+    from .encoders import LSTMStateEncoder
+
+    return (_lstm_backward if isinstance(enc, LSTMStateEncoder) else _gru_backward)(enc, s, d_out, G)
+
+
 def _conv1d_backward(conv, d_out4, x4, d_in_residual4, G):
     """Conv1d(k=1) viewed as a 1x1 conv over (rows, C, 1, P): returns d(x) (+ residual)."""
     O, Cc = conv.weight.shape[0], conv.weight.shape[1]
@@ -228,8 +254,8 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     d_out_dep = net.depth_linear[1].out_features
     m_out = net.map_linear[1].out_features
 
-    # ---- second GRU and its input compression ---------------------------------------------------
-    d_c2 = _gru_backward(net.second_state_encoder, S["g2"], d_feats.contiguous(), G)
+    # ---- second state encoder and its input compression ---------------------------------------------------
+    d_c2 = _state_encoder_backward(net.second_state_encoder, S["g2"], d_feats.contiguous(), G)
     d_pre = ops.relu_bwd(d_c2, S["c2"])
     sc = net.second_state_compress[0]
     G[sc.weight] = ops.linear_bwd_weight(d_pre, x2)
@@ -278,8 +304,8 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     d_state = dx2[:, :H]
     ops.linear_bwd_input(dq1, net.state_q.weight, out=d_state, accumulate=True)
 
-    # ---- first GRU ----------------------------------------------------------------------------------
-    d_state_in = _gru_backward(net.state_encoder, S["g1"], d_state, G)  # (rows, 416)
+    # ---- first state encoder ----------------------------------------------------------------------------------
+    d_state_in = _state_encoder_backward(net.state_encoder, S["g1"], d_state, G)  # (rows, 416)
     emb = net.prev_action_embedding
     G[emb.weight] = ops.prev_action_embed_bwd(S["prev_actions"], S["masks"], d_state_in[:, d_out_dep + m_out:],
                                               dx2[:, o_prev:], emb.num_embeddings)
