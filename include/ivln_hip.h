@@ -714,6 +714,21 @@ typedef struct ivln_cma_step_desc {
 } ivln_cma_step_desc;
 int64_t ivln_cma_step_ws_floats(int rows, int L, int P, int H);
 int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream);
+/* The same head for STATE_ENCODER.rnn_type LSTM (two masked LSTM encoders, csrc/lstm_state.hip's arithmetic: gates
+ * i, f, g, o; h' = h * mask, c' = c * mask; pre = (W_ih x + b_ih) + (W_hh h' + b_hh)): LSTM-1 -> text attention ->
+ * depth + map attention -> compress -> LSTM-2, again five dependent launches behind one call, the three middle phases
+ * being the GRU form's.  It takes the SAME descriptor, read as follows: w_ih1 (4H x (d_out+m_out+E)), w_hh1 / w_ih2 /
+ * w_hh2 (4H x H), the four biases 4H long; h_in / h_out are (rows, 4, H) views [h1 | c1 | h2 | c2] with row strides
+ * ld_h / ld_ho >= 4H.  h1' -> x2[:, :H] and slot 0, c1' -> slot 1, h2' -> feats and slot 2, c2' -> slot 3.  Everything
+ * else (folds, operands, x2, feats) as above.  ws: ivln_cma_step_lstm_ws_floats() floats.  Its layout is a superset of
+ * the GRU form's: [logits | S | rows x 3H, unused here | c2], which the shared phase kernels address as they always did,
+ * followed by the hidden half of LSTM-2 (rows x 4H); ivln_cma_step_lstm_ws_floats = ivln_cma_step_ws_floats + that
+ * region, rounded up to 128-byte lines.  Same envelope as ivln_cma_step_fwd, and in addition IVLN_E_UNSUPPORTED for ld_ho % 4 != 0 and
+ * IVLN_E_INVALID for a NULL h_in / h_out, a row stride below 4H, or h_in / h_out row ranges that overlap (every
+ * workgroup reads whole rows of h_in while others write h_out).  Nothing is launched when a code other than IVLN_OK /
+ * IVLN_E_HIP is returned. */
+int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H);
+int ivln_cma_step_lstm_fwd(const ivln_cma_step_desc* d, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward / loss / optimizer kernels of the DAgger update (csrc/train_ops.hip): replace the
@@ -830,8 +845,8 @@ int ivln_dtw_symmetric1(const double* a, int n, const double* b, int m, int dim,
  * batch-first state (N, 2, H) slot 0 is h and slot 1 is c.  All fp32.  H % 4 == 0, else IVLN_E_INVALID.
  *   h' = h * mask, c' = c * mask;  gates = W_ih x + b_ih + W_hh h' + b_hh
  *   c_t = s(f) c' + s(i) tanh(g);  h_t = s(o) tanh(c_t)
- * There is no single-launch (persistent) form and no fused-head form of this encoder: a sequence is one launch per
- * timestep, and ivln_cma_step_fwd stays GRU arithmetic.
+ * There is no single-launch (persistent) form of this encoder: a sequence is one launch per timestep.  The fused
+ * rollout head with two such encoders is ivln_cma_step_lstm_fwd (above); ivln_cma_step_fwd stays GRU arithmetic.
  * ------------------------------------------------------------------------------------------ */
 /* One masked step (RNNStateEncoder single_forward, or one step of seq_forward) for `rows` states.  Input: x (rows, I)
  * row stride ldx with w_ih (4H, I) / b_ih (4H), or gi_pre (rows, 4H) row stride ldgi = W_ih x + b_ih precomputed

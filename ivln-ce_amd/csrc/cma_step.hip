@@ -39,6 +39,17 @@
 // (<= 64 batch rows against 512-1536 outputs, a GEMV per row).  Bound: L2 -> CU latency per phase, not FLOPs.
 // (A first version gave each WAVE an output and looped over rows in registers on a 128-workgroup grid: 50 us slower
 // per step than the unfused chain - per-wave serial latency, not bandwidth, is what these phases are made of.)
+//
+// STATE_ENCODER.rnn_type LSTM (ivln_cma_step_lstm_fwd, second half of the file): the same five launches with two masked
+// LSTM encoders (csrc/lstm_state.hip's arithmetic and association; gates i, f, g, o; state (rows, 4, H) = [h1 | c1 | h2 | c2]):
+//
+//   state, c1' = LSTM1([dep_in | map_in | prev], h1 * mask, c1 * mask)      text / dep' / map' as above
+//   feats, c2' = LSTM2(ReLU(W_c [state | text | dep' | map' | prev] + b_c), h2 * mask, c2 * mask)
+//
+// The folds, the S tables, text logits, the three attentions and compress do not depend on the cell: phases 2 and 4 are
+// the SAME kernels, phase 3 the same device function.  Phases 1 and 5 and the off-chain hidden half of the second encoder
+// (now rows x 4H) have an LSTM unit with gru_unit's work split; the GRU kernels are instantiated from the code they
+// always were.  No barrier, no spin, no counter here either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -385,6 +396,143 @@ void launch_cma(const Desc& D, int mode, hipStream_t s) {
     hipLaunchKernelGGL((k_cma_phase<5, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
 }
 
+// ======== LSTM state encoders (STATE_ENCODER.rnn_type LSTM) ===============================================
+// The same five phases with LSTM arithmetic in the two encoders.  Phases 2 and 4 ARE the kernels above and phase 3's
+// main part is `phase3`: text logits, the three attentions and compress do not know the cell type, and they address the
+// scratch by the layout above.  What differs: four gate rows per unit (torch's order i, f, g, o), a cell state beside
+// the hidden state - the state is (rows, 4, H) = [h1 | c1 | h2 | c2] - and a hidden half of rows x 4H floats, which has a
+// region of its own BEHIND the layout above (the rows x 3H region in the middle stays unused here, so that the shared
+// kernels find c2 where they look for it).
+__device__ __forceinline__ float* ws_gh2_lstm(const Desc& D) { return ws_c2(D) + al32((int64_t)D.rows * D.H); }
+
+__device__ __forceinline__ float fma4(const float4 w, const float4 v, float a) {
+    a = fmaf(w.x, v.x, a);
+    a = fmaf(w.y, v.y, a);
+    a = fmaf(w.z, v.z, a);
+    return fmaf(w.w, v.w, a);
+}
+
+// the four gate rows of unit j against one row of x (scaled by mk: the mask of the incoming state, 1 for an input):
+// one pass over K, each 16-byte piece of x loaded once for the four rows (the loop of k_lstm_step, lstm_state.hip)
+template <int LPR>
+__device__ __forceinline__ void lstm_dot4(const float* __restrict__ w, int j, int H, int K, const float* __restrict__ x,
+                                          float mk, int l, float (&a)[4]) {
+    for (int k = l * 4; k < K; k += LPR * 4) {
+        float4 xv = *reinterpret_cast<const float4*>(x + k);
+        xv.x *= mk, xv.y *= mk, xv.z *= mk, xv.w *= mk;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) a[g] = fma4(*reinterpret_cast<const float4*>(w + ((int64_t)g * H + j) * K + k), xv, a[g]);
+    }
+}
+
+// ---- one masked LSTM unit j for all rows (the work split of gru_unit) ---------------------------------
+// h_in / c_in: the encoder's two slots of the incoming state (row stride ld_h); gh_pre != nullptr: the hidden-side
+// pre-activations W_hh h' + b_hh were computed earlier (side_gh2_lstm) and h_in is not read.  h_t -> out1 and hs_out,
+// c_t -> cs_out (the encoder's two slots of the outgoing state, row stride ld_ho).  Association as in k_lstm_step:
+// pre = (W_ih x + b_ih) + (W_hh h' + b_hh), the mask applied to h and c BEFORE they are used.
+template <int LPR>
+__device__ __forceinline__ void lstm_unit(const Desc& D, int j, const float* x, int64_t ldx, int I, const float* w_ih,
+                                          const float* w_hh, const float* b_ih, const float* b_hh, const float* h_in,
+                                          const float* c_in, const float* gh_pre, float* out1, int64_t ld1, float* hs_out,
+                                          float* cs_out) {
+    constexpr int RPB = CT / LPR;
+    const int H = D.H;
+    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
+    for (int r0 = 0; r0 < D.rows; r0 += RPB) {
+        const int row = r0 + rr;
+        const bool ok = row < D.rows;
+        const int rc = ok ? row : 0;
+        const float mk = D.mask[rc] ? 1.f : 0.f;
+        float ai[4] = {0.f, 0.f, 0.f, 0.f}, ah[4] = {0.f, 0.f, 0.f, 0.f};
+        lstm_dot4<LPR>(w_ih, j, H, I, x + (int64_t)rc * ldx, 1.f, l, ai);
+        if (!gh_pre) lstm_dot4<LPR>(w_hh, j, H, H, h_in + (int64_t)rc * D.ld_h, mk, l, ah);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            ai[g] = lpr_sum<LPR>(ai[g]);
+            if (!gh_pre) ah[g] = lpr_sum<LPR>(ah[g]);
+        }
+        if (l == 0 && ok) {
+            float pre[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float gi = ai[g] + b_ih[g * H + j];
+                pre[g] = gi + (gh_pre ? gh_pre[(int64_t)row * 4 * H + g * H + j] : ah[g] + b_hh[g * H + j]);
+            }
+            const float cp = c_in[(int64_t)row * D.ld_h + j] * mk;
+            const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf(pre[2]), og = sigmoidf_(pre[3]);
+            const float ct = fg * cp + ig * gg;
+            const float ht = og * tanhf(ct);
+            st_pub(out1 + (int64_t)row * ld1 + j, ht);
+            st_pub(hs_out + (int64_t)row * D.ld_ho + j, ht);
+            st_pub(cs_out + (int64_t)row * D.ld_ho + j, ct);
+        }
+    }
+}
+
+// ---- LSTM-1: state slots 0 (h1) and 1 (c1) -------------------------------------------------------------
+template <int LPR>
+__device__ void phase1_lstm(const Desc& D, int wg, int nwg) {
+    const int sin_w = D.d_out + D.m_out + D.E;
+    for (int j = wg; j < D.H; j += nwg)
+        lstm_unit<LPR>(D, j, D.state_in, sin_w, sin_w, D.w_ih1, D.w_hh1, D.b_ih1, D.b_hh1, D.h_in, D.h_in + D.H, nullptr,
+                       D.x2, D.x2w, D.h_out, D.h_out + D.H);
+}
+
+// ---- hidden half of LSTM-2: gh2[r][g*H + j] = W_hh2[g*H + j] . (h2[r] * mask[r]) + b_hh2, h2 = state slot 2; rides in
+// the attention phase's launch as side_gh2 does ----
+template <int LPR>
+__device__ void side_gh2_lstm(const Desc& D, int wg, int nwg) {
+    constexpr int RPB = CT / LPR;
+    const int H = D.H;
+    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
+    for (int j = wg; j < H; j += nwg) {
+        for (int r0 = 0; r0 < D.rows; r0 += RPB) {
+            const int row = r0 + rr;
+            const bool ok = row < D.rows;
+            const int rc = ok ? row : 0;
+            const float mk = D.mask[rc] ? 1.f : 0.f;
+            float ah[4] = {0.f, 0.f, 0.f, 0.f};
+            lstm_dot4<LPR>(D.w_hh2, j, H, H, D.h_in + 2 * H + (int64_t)rc * D.ld_h, mk, l, ah);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float v = lpr_sum<LPR>(ah[g]);
+                if (l == 0 && ok) st_pub(ws_gh2_lstm(D) + (int64_t)row * 4 * H + g * H + j, v + D.b_hh2[g * H + j]);
+            }
+        }
+    }
+}
+
+// ---- LSTM-2: input half here, hidden half from side_gh2_lstm; state slots 2 (h2) and 3 (c2) ------------
+template <int LPR>
+__device__ void phase5_lstm(const Desc& D, int wg, int nwg) {
+    for (int j = wg; j < D.H; j += nwg)
+        lstm_unit<LPR>(D, j, ws_c2(D), D.H, D.H, D.w_ih2, D.w_hh2, D.b_ih2, D.b_hh2, D.h_in + 2 * D.H, D.h_in + 3 * D.H,
+                       ws_gh2_lstm(D), D.feats, D.H, D.h_out + 2 * D.H, D.h_out + 3 * D.H);
+}
+
+// the three launches that hold cell arithmetic; phases 2 and 4 are k_cma_phase<2> / <4>
+template <int PH, int LPR>
+__global__ __launch_bounds__(CT) void k_cma_lstm_phase(const Desc D, int main) {
+    const int wg = blockIdx.x, nwg = gridDim.x;
+    if constexpr (PH == 1) phase1_lstm<LPR>(D, wg, nwg);
+    if constexpr (PH == 3) {
+        if (wg < main) phase3(D, wg, main);
+        else side_gh2_lstm<LPR>(D, wg - main, nwg - main);
+    }
+    if constexpr (PH == 5) phase5_lstm<LPR>(D, wg, nwg);
+}
+
+template <int LPR>
+void launch_cma_lstm(const Desc& D, hipStream_t s) {
+    const int tiles = (D.L + 15) / 16;
+    const int chunks = (D.Ct + D.d_out + D.m_out) / 16;
+    hipLaunchKernelGGL((k_cma_lstm_phase<1, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+    hipLaunchKernelGGL((k_cma_phase<2, LPR>), dim3(D.rows * tiles + D.rows * D.L), dim3(CT), 0, s, D, D.rows * tiles);
+    hipLaunchKernelGGL((k_cma_lstm_phase<3, LPR>), dim3(D.rows * chunks + D.H), dim3(CT), 0, s, D, D.rows * chunks);
+    hipLaunchKernelGGL((k_cma_phase<4, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+    hipLaunchKernelGGL((k_cma_lstm_phase<5, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+}
+
 }  // namespace
 
 extern "C" {
@@ -408,6 +556,36 @@ int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
     if (D.rows <= 4) launch_cma<64>(D, mode, s);
     else if (D.rows <= 8) launch_cma<32>(D, mode, s);
     else launch_cma<16>(D, mode, s);
+    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+}
+
+int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H) {
+    // the layout above (its gh2 region unused) + the LSTM hidden half (rows*4H)
+    return ivln_cma_step_ws_floats(rows, L, P, H) + al32((int64_t)rows * 4 * H);
+}
+
+int ivln_cma_step_lstm_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
+    (void)mode;
+    if (!d || d->rows <= 0 || !d->ws || !d->x2 || !d->feats || !d->h_in || !d->h_out) return IVLN_E_INVALID;
+    if (d->L <= 0 || d->L > MAX_L || d->P <= 0 || d->P > 16) return IVLN_E_UNSUPPORTED;
+    if (d->H <= 0 || (d->H & 63) || (d->Hq & 15) || (d->Ct & 15) || (d->d_out & 15) || (d->m_out & 15)) return IVLN_E_UNSUPPORTED;
+    const int sin_w = d->d_out + d->m_out + d->E;
+    if ((sin_w & 3) || (d->x2w & 3) || (d->ld_h & 3) || (d->ld_ho & 3) ||
+        d->x2w != d->H + d->Ct + d->d_out + d->m_out + d->E)
+        return IVLN_E_UNSUPPORTED;
+    // every workgroup reads whole rows of h_in while others write h_out: the (rows, 4, H) views must not share memory
+    const int64_t G = (int64_t)4 * d->H;
+    if (d->ld_h < G || d->ld_ho < G) return IVLN_E_INVALID;
+    const float *in0 = d->h_in, *in1 = d->h_in + (int64_t)(d->rows - 1) * d->ld_h + G;
+    const float *out0 = d->h_out, *out1 = d->h_out + (int64_t)(d->rows - 1) * d->ld_ho + G;
+    if ((uintptr_t)in0 < (uintptr_t)out1 && (uintptr_t)out0 < (uintptr_t)in1) return IVLN_E_INVALID;
+    Desc D = *d;
+    if (D.Mq_img <= 0) D.Mq_img = (int64_t)(D.H + 1) * D.L;
+    if (D.TQb_img <= 0) D.TQb_img = (int64_t)D.Hq * D.L;
+    hipStream_t s = (hipStream_t)stream;
+    if (D.rows <= 4) launch_cma_lstm<64>(D, s);
+    else if (D.rows <= 8) launch_cma_lstm<32>(D, s);
+    else launch_cma_lstm<16>(D, s);
     return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
 }
 

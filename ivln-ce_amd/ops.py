@@ -1099,8 +1099,8 @@ class CmaStepDesc(C.Structure):
     ]
 
 
-# rollout head: 0 = ivln_cma_step_fwd (folded operands, five phase kernels), -1 = the unfused chain of ten separate ops
-# (A/B switch IVLN_CMA_STEP_MODE; measured 0.977 vs 0.988 ms per 4-env step)
+# rollout head: 0 = ivln_cma_step_fwd (folded operands, five phase kernels; ivln_cma_step_lstm_fwd for LSTM encoders),
+# -1 = the unfused chain of ten separate ops (A/B switch IVLN_CMA_STEP_MODE; measured 0.977 vs 0.988 ms per 4-env GRU step)
 CMA_STEP_MODE = int(os.environ.get("IVLN_CMA_STEP_MODE", "0"))
 _cma_ws = {}
 CMA_WS_OWNER = 0  # graphed.GraphedRollout sets its own id while it warms up / captures: every runner owns a workspace
@@ -1128,14 +1128,45 @@ def cma_step_ws(rows, L, P, H, device):
 
 
 def release_cma_ws(owner):
-    for k in [k for k in _cma_ws if k[-1] == owner]:
-        del _cma_ws[k]
+    for ws in (_cma_ws, _cma_lstm_ws):
+        for k in [k for k in ws if k[-1] == owner]:
+            del ws[k]
 
 
 def cma_step(d: CmaStepDesc, mode=None):
     L_ = _L()
     L_.ivln_cma_step_fwd.argtypes = [C.POINTER(CmaStepDesc), i32, vp]
     check(L_.ivln_cma_step_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_fwd")
+
+
+# the same head with LSTM state encoders (ivln_cma_step_lstm_fwd): its own entry point and its own scratch - nothing is
+# shared with the GRU form, whose launches and buffers stay what they are beside an LSTM policy in the same process.
+# CMA_STEP_MODE < 0 turns both forms off.
+_cma_lstm_ws = {}
+
+
+def cma_step_lstm_ws(rows, L, P, H, device):
+    """Scratch of the fused LSTM head, one per (device, shape, OWNER) as `cma_step_ws` keeps it for the GRU form (same
+    ownership and capture rules); larger than that one by the rows x 4H hidden half of the second encoder."""
+    L_ = _L()
+    L_.ivln_cma_step_lstm_ws_floats.restype = i64
+    L_.ivln_cma_step_lstm_ws_floats.argtypes = [i32, i32, i32, i32]
+    n = L_.ivln_cma_step_lstm_ws_floats(rows, L, P, H)
+    key = (str(device), rows, L, P, H, CMA_WS_OWNER)
+    w = _cma_lstm_ws.get(key)
+    if w is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.IvlnError("cma_step_lstm workspace must exist before stream capture (run one warm-up step first)")
+        w = torch.zeros(n, dtype=torch.float32, device=device)
+        _cma_lstm_ws[key] = w
+    return w
+
+
+def cma_step_lstm(d: CmaStepDesc, mode=None):
+    """`d` read the LSTM way (include/ivln_hip.h): 4H weight rows, h_in / h_out (rows, 4, H) views [h1 | c1 | h2 | c2]."""
+    L_ = _L()
+    L_.ivln_cma_step_lstm_fwd.argtypes = [C.POINTER(CmaStepDesc), i32, vp]
+    check(L_.ivln_cma_step_lstm_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_lstm_fwd")
 
 
 WEIGHT_EPOCH = 0  # bumped by FlatAdam.step(): kernels update parameters through raw pointers, which

@@ -16,8 +16,8 @@ from torch import Tensor
 
 from . import ops
 from .aux_losses import AuxLosses
-from .encoders import (InstructionEncoder, RNNStateEncoder, SemanticMapEncoder, VlnResnetDepthEncoder,
-                       build_rnn_state_encoder)
+from .encoders import (InstructionEncoder, LSTMStateEncoder, RNNStateEncoder, SemanticMapEncoder,
+                       VlnResnetDepthEncoder, build_rnn_state_encoder)
 from .registry import baseline_registry
 
 try:  # pragma: no cover
@@ -169,6 +169,16 @@ class MapCMANet(Net):
         """Both state encoders are GRUs: what the fused recurrent head (ivln_cma_step_fwd, GRU arithmetic) requires."""
         return isinstance(self.state_encoder, RNNStateEncoder) and isinstance(self.second_state_encoder, RNNStateEncoder)
 
+    @property
+    def fused_head_form(self):
+        """The form of the fused recurrent head (csrc/cma_step.hip) the two state encoders allow: "gru"
+        (ivln_cma_step_fwd), "lstm" (ivln_cma_step_lstm_fwd), or None - the unfused chain."""
+        if self._gru_encoders:
+            return "gru"
+        if isinstance(self.state_encoder, LSTMStateEncoder) and isinstance(self.second_state_encoder, LSTMStateEncoder):
+            return "lstm"
+        return None
+
     @staticmethod
     def _state_slot(states, first, n):
         """The n recurrent layers from `first` on of a batch-first (N, L, H) state, as an encoder takes them: (N, H) for
@@ -197,14 +207,16 @@ class MapCMANet(Net):
     def prepare_capture(self, example_obs):
         """Create everything the rollout step caches lazily BEFORE a stream capture (graphed.py): a buffer born inside
         a capture lives in that graph's private pool and must not survive in a process-wide cache."""
-        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or not self._gru_encoders:
+        form = self.fused_head_form
+        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or form is None:
             return
         rows, L = example_obs["instruction"].shape[0], example_obs["instruction"].shape[1]
         P = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         if P > 16 or L > 512:
             return  # outside the fused head's envelope: forward_hip takes the unfused chain
         self._cma_fold_weights()
-        ops.cma_step_ws(rows, L, P, self._hidden_size, example_obs["instruction"].device)
+        ws = ops.cma_step_lstm_ws if form == "lstm" else ops.cma_step_ws
+        ws(rows, L, P, self._hidden_size, example_obs["instruction"].device)
 
     def _init_layers(self):
         if self.model_config.PROGRESS_MONITOR.use:
@@ -241,13 +253,15 @@ class MapCMANet(Net):
         dl, ml = self.depth_linear[1], self.map_linear[1]
         o_txt, o_dep, o_map, o_prev = H, H + 256, H + 256 + d_out, H + 256 + d_out + m_out
 
-        # The fused recurrent head (ivln_cma_step_fwd) wants the instruction branch to emit the folded [Mq | TQb] operand
-        # instead of text_k, so its eligibility is decided HERE, from shapes known before any branch runs (the encoders'
-        # static output shapes, the token axis, the widths' divisibility rules of csrc/cma_step.hip) - anything
-        # outside the kernel's envelope takes the unfused chain with a real text_k.
+        # The fused recurrent head (ivln_cma_step_fwd; ivln_cma_step_lstm_fwd with LSTM encoders - the fold does not depend
+        # on the cell) wants the instruction branch to emit the folded [Mq | TQb] operand instead of text_k, so its
+        # eligibility is decided HERE, from shapes known before any branch runs (the encoders' static output shapes, the
+        # token axis, the widths' divisibility rules of csrc/cma_step.hip) - anything outside the kernel's envelope
+        # takes the unfused chain with a real text_k.
         P_static = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         L_static = observations["instruction"].shape[-1] if "instruction" in observations else 0
-        fused_head = (save is None and ops.CMA_STEP_MODE >= 0 and self._gru_encoders
+        head_form = self.fused_head_form
+        fused_head = (save is None and ops.CMA_STEP_MODE >= 0 and head_form is not None
                       and not (mc.ablate_instruction or mc.ablate_depth or mc.ablate_map)
                       and P_static <= 16 and 0 < L_static <= 512
                       and self.map_encoder.output_shape[1] * self.map_encoder.output_shape[2] == P_static
@@ -410,7 +424,8 @@ class MapCMANet(Net):
             rnn_out = torch.empty_like(rnn_states)
         if fused_head and P <= 16 and L <= 512 and tk.shape[1] == H + 1 + h2:
             # GRU-1 -> text attention -> depth / map attention -> compress -> GRU-2 as one C-ABI call (five phase kernels,
-            # csrc/cma_step.hip); `tk` holds the folded [Mq | TQb] operand here
+            # csrc/cma_step.hip); `tk` holds the folded [Mq | TQb] operand here.  With LSTM encoders the same descriptor
+            # goes to the LSTM form: 4H weight rows, and the (rows, 4, H) states [h1 | c1 | h2 | c2]
             feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
             g1, g2, sc = self.state_encoder.rnn, self.second_state_encoder.rnn, self.second_state_compress[0]
             d = ops.CmaStepDesc()
@@ -426,9 +441,13 @@ class MapCMANet(Net):
             d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2 = (ops.dptr(g2.weight_ih_l0), ops.dptr(g2.weight_hh_l0),
                                                   ops.dptr(g2.bias_ih_l0), ops.dptr(g2.bias_hh_l0))
             d.x2, d.h_out, d.ld_ho, d.feats = ops.dptr(x2), ops.dptr(rnn_out), rnn_out.stride(0), ops.dptr(feats)
-            ws = ops.cma_step_ws(rows, L, P, H, dev)
-            d.ws = ops.dptr(ws)
-            ops.cma_step(d)
+            if head_form == "lstm":
+                d.ws = ops.dptr(ops.cma_step_lstm_ws(rows, L, P, H, dev))
+                ops.cma_step_lstm(d)
+            else:
+                ws = ops.cma_step_ws(rows, L, P, H, dev)
+                d.ws = ops.dptr(ws)
+                ops.cma_step(d)
             return feats, rnn_out
         s_g1 = {} if save is not None else None
         s_g2 = {} if save is not None else None
