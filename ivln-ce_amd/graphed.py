@@ -4,11 +4,15 @@ them) and replayed per env step.  Inside the capture the three independent branc
 on forked streams: instruction bi-LSTM || mapper -> semantic-map CNN || DD-PPO depth ResNet, joined
 before the recurrent/attention head.  At 4-8 envs the step is ~170 launches of a few microseconds
 each: replay removes the per-launch host cost and the fork overlaps the latency-bound branches.
+The runner hands the net its side streams and output buffers as arguments (`MapCMANet.forward_hip`); in
+split mode it captures the net's three stages (`stage_depth`, `stage_pre`, `stage_post`) as graphs of
+their own, keeps what each returns and passes it to the next - none of it is stored on the net.
 
 Two graphs are captured with the recurrent state / previous action ping-ponging between two
 buffer sets (graph 0: A -> B, graph 1: B -> A), so no state copies are needed between steps; the
 only per-step copies are the observation tensors the step actually reads.
 """
+import contextlib
 import os
 from typing import Dict
 
@@ -16,6 +20,7 @@ import torch
 
 from . import mapping as _mapping
 from . import ops
+from .policy import MapCMANet, SplitStep
 
 _streams = {}
 
@@ -102,7 +107,9 @@ class _CutCapture:
 
 
 class GraphedRollout:
-    """mapper + `policy.act` of one env step as replayable hipGraphs (see the module docstring).  Side effect of the
+    """mapper + the policy's step as replayable hipGraphs (see the module docstring).  The step is `net.forward_hip` or its
+    three stages, then `ILPolicy._act`, called directly and not through `policy.act`: `MapCMANet.forward`'s aux-loss tail,
+    forward hooks on the net and an `act` overridden in a subclass are no part of a captured step.  Side effect of the
     split capture: it fixes how the pieces that run beside each other are launched - the gt-semantics mapper narrow
     (`MappingModule.set_launch_width`), the policy's depth encoder as its launch-saving chain when it is the critical
     path and as conv + GroupNorm pairs when RedNet is (`visual_encoder.latency_bound`); eager calls afterwards run the
@@ -115,6 +122,9 @@ class GraphedRollout:
         retired after a time-out: the launch chain has never run on the capture streams, and its per-stream workspaces must
         exist before a capture can record launches that use them) while the world cloud must not be stepped."""
         self.policy = policy
+        self._staged = isinstance(policy.net, MapCMANet)  # (its step takes streams and output buffers; other nets: net())
+        if streams == "split" and not self._staged:
+            raise TypeError(f"streams='split' needs MapCMANet's stages; {type(policy.net).__name__} has none")
         self.transforms = list(obs_transforms)
         self._warmup_mapper = warmup_mapper
         self.deterministic = deterministic
@@ -167,39 +177,40 @@ class GraphedRollout:
 
     def _body(self, src: int):
         dst = src ^ 1
-        cur = torch.cuda.current_stream()
         batch = dict(self.static)
         net = self.policy.net
         if self.side is not None:
-            s_txt, s_map = self.side
-            s_map.wait_stream(cur)
+            self.side[1].wait_stream(torch.cuda.current_stream())
             # hipGraph replay submits nodes in capture order (~3 us of host time each), so the critical
             # path - the 107-kernel depth ResNet chain - is captured FIRST; the policy then takes the
             # cached `depth_features` path (resnet_encoders.py:92-95)
             with torch.no_grad():
                 batch["depth_features"] = net.depth_encoder.visual_encoder(batch)
-            with torch.cuda.stream(s_map):  # the mapper feeds only the map CNN, which stays on s_map
+            with torch.cuda.stream(self.side[1]):  # the mapper feeds only the map CNN, which stays on that stream (s_map)
                 for t in self.transforms:
                     batch = t(batch)
-            net._side_streams = self.side
         else:
             for t in self.transforms:
                 batch = t(batch)
-        net._rnn_out_buffer = self.rnn[dst]
-        self.policy._action_out_buffer = self.prev[dst] if self._direct_actions else None
         self._last_batch = batch
-        try:
-            with torch.no_grad():
-                actions, rnn = self.policy.act(batch, self.rnn[src], self.prev[src], _policy_masks(batch),
-                                               deterministic=self.deterministic)
-                if actions.data_ptr() != self.prev[dst].data_ptr():
-                    self.prev[dst].copy_(actions)
-                if rnn.data_ptr() != self.rnn[dst].data_ptr():
-                    self.rnn[dst].copy_(rnn)
-        finally:
-            net._side_streams = None
-            net._rnn_out_buffer = None
-            self.policy._action_out_buffer = None
+        args = self._step_args(batch, src)
+        with torch.no_grad():
+            if self._staged:
+                feats, rnn = net.forward_hip(*args, side_streams=self.side, rnn_out=self.rnn[dst])
+            else:  # (what policy.act calls)
+                feats, rnn = net(*args)
+            self._finish(feats, rnn, batch, dst)
+
+    def _step_args(self, batch, src):
+        return batch, self.rnn[src], self.prev[src], _policy_masks(batch)
+
+    def _finish(self, feats, rnn, batch, dst):
+        """Action head behind the net; results end in buffer set `dst`: copied only where no kernel wrote them in place."""
+        actions = self.policy._act(feats, self.deterministic, batch, out=self.prev[dst] if self._direct_actions else None)
+        if actions.data_ptr() != self.prev[dst].data_ptr():
+            self.prev[dst].copy_(actions)
+        if rnn.data_ptr() != self.rnn[dst].data_ptr():
+            self.rnn[dst].copy_(rnn)
 
     # ---- split mode: three graphs per step on two streams ---------------------------------------
     #   gA  (side stream): depth ResNet, its k/v projection, depth_linear   (60 % of the step's kernel
@@ -215,79 +226,53 @@ class GraphedRollout:
         main = torch.cuda.current_stream()
 
         B = self.rnn[0].shape[0]
-        d_out, m_out = net.depth_linear[1].out_features, net.map_linear[1].out_features
-        E, H = net.prev_action_embedding.embedding_dim, net._hidden_size
-        self._persist = dict(
-            state_in=torch.empty((B, d_out + m_out + E), dtype=torch.float32, device=dev),
-            x2=torch.empty((B, H + net.instruction_encoder.output_size + d_out + m_out + E), dtype=torch.float32,
-                           device=dev),
-        )
+        predicted = any(getattr(t, "predicted_semantics", False) for t in self.transforms)
+        # the buffers the three stages share; with predicted semantics the instruction encoder leaves RedNet's stream for the
+        # side graph, otherwise it is the last branch of gB1 (MapCMANet.stage_pre)
+        self._step = step = SplitStep(*net.step_geometry.buffers(B, dev), txt_with_dep=predicted, txt_last=True)
 
         from . import rednet as _rednet
 
-        def run_A():
-            net._stage, net._persist = "dep", self._persist
-            try:
-                with torch.no_grad():
-                    batch = dict(self.static)
-                    if self._prefix:
-                        # the mapper's label-free half (transforms, min / max, keep-highest arg-max: depth and pose only)
-                        # rides at the head of the side graph, beside RedNet, instead of behind it on the critical path
-                        for t in self.transforms:
-                            t.begin_maps(batch)
-                        _rednet._stage_done("mapper_begin")
-                    net.forward_hip(batch, self.rnn[0], self.prev[0], _policy_masks(batch))
-            finally:
-                net._stage = net._persist = None
+        def run_A():  # -> (depth result, instruction result or None)
+            with torch.no_grad():
+                batch = dict(self.static)
+                if self._prefix:
+                    # the mapper's label-free half (transforms, min / max, keep-highest arg-max: depth and pose only)
+                    # rides at the head of the side graph, beside RedNet, instead of behind it on the critical path
+                    for t in self.transforms:
+                        t.begin_maps(batch)
+                    _rednet._stage_done("mapper_begin")
+                return net.stage_depth(*self._step_args(batch, 0), step)
 
-        def run_B1(src):
+        def run_B1(src, txt):  # -> (batch, (instruction result, map result))
             batch = dict(self.static)
             for t in self.transforms:
                 batch = t.finish_maps(batch) if self._prefix else t(batch)
-            net._stage, net._persist = "pre", self._persist
-            try:
-                with torch.no_grad():
-                    net.forward_hip(batch, self.rnn[src], self.prev[src], _policy_masks(batch))
-            finally:
-                net._stage = net._persist = None
-            return batch
+            with torch.no_grad():
+                return batch, net.stage_pre(*self._step_args(batch, src), step, txt)
 
-        def run_B2(src, batch):
-            dst = src ^ 1
+        def run_B2(src, dep, batch, pre):
             batch = dict(batch)
-            net._stage, net._persist = "post", self._persist
-            net._rnn_out_buffer = self.rnn[dst]
-            self.policy._action_out_buffer = self.prev[dst] if self._direct_actions else None
-            try:
-                with torch.no_grad():
-                    actions, rnn = self.policy.act(batch, self.rnn[src], self.prev[src], _policy_masks(batch),
-                                                   deterministic=self.deterministic)
-                    if actions.data_ptr() != self.prev[dst].data_ptr():
-                        self.prev[dst].copy_(actions)
-                    if rnn.data_ptr() != self.rnn[dst].data_ptr():
-                        self.rnn[dst].copy_(rnn)
-            finally:
-                net._stage = net._persist = None
-                net._rnn_out_buffer = None
-                self.policy._action_out_buffer = None
+            with torch.no_grad():
+                feats, rnn = net.stage_post(*self._step_args(batch, src), step, dep, pre, rnn_out=self.rnn[src ^ 1])
+                self._finish(feats, rnn, batch, src ^ 1)
 
         # With predicted semantics the depth encoder is NOT the critical path (RedNet is): its launch-saving chain of 16
         # partial slabs per conv would only take HBM bandwidth from RedNet (6.84 vs 6.69 ms per step at 8 envs), so it
         # runs the conv + GroupNorm pairs there.  (Decided before the warm-up: every lazily built cache of the path
         # that will be captured has to exist before the capture.)
         venc = getattr(getattr(net, "depth_encoder", None), "visual_encoder", None)
-        predicted = any(getattr(t, "predicted_semantics", False) for t in self.transforms)
         # With predicted semantics gB1 is cut behind one of RedNet's stages (rednet.STAGE_HOOK) and gA is released by an event
         # recorded at the cut: the depth encoder's ~110 small launches then run beside RedNet's pixel-starved deep stages,
         # whose grids leave CUs idle, instead of taking CUs from the chip-filling first ones (round 5: gB1 alone 3242 us,
         # 3562 us with gA started at t = 0; round 6, profiles/r06_split_probe_start.txt: gB1 ends at 3477 / 3461 / 3432 us with
         # the cut behind layer 2 / 3 / 4).  IVLN_PRED_DEPTH_START: stage name, or "0" = no cut (gA starts with the step).
-        self._cut_stage = os.environ.get("IVLN_PRED_DEPTH_START", "layer3") if predicted else "0"
-        if self._cut_stage in ("0", "", "none"):
-            self._cut_stage = None
+        self._cut_at = os.environ.get("IVLN_PRED_DEPTH_START", "layer3") if predicted else "0"
+        if self._cut_at in ("0", "", "none"):
+            self._cut_at = None
         # ... and the mapper's label-free half moves to the head of gA (MappingModule.begin / finish, ivln_mapper_step_begin /
         # _finish): gB1 is cut a second time where the labels exist, and waits there for the event recorded behind the prefix
-        self._prefix = bool(self._cut_stage) and os.environ.get("IVLN_MAPPER_PREFIX", "1") != "0" and _mapping.STEP_POSED and all(
+        self._prefix = bool(self._cut_at) and os.environ.get("IVLN_MAPPER_PREFIX", "1") != "0" and _mapping.STEP_POSED and all(
             hasattr(t, "begin_maps") and type(t).__name__.endswith("IterativeMapper") for t in self.transforms)
         # (the side graph cut in two - its first part beside RedNet's early stages, the second beside its late ones, pausing
         #  during the pixel-starved middle - was built and measured in round 6: gB1 ends at 3453-3462 us against 3408, whatever
@@ -305,15 +290,13 @@ class GraphedRollout:
             venc.no_persistent = pd == "chain"
             if pd in ("chain", "net"):
                 venc.latency_bound = True
-        net._txt_with_dep = predicted  # ... and the instruction encoder leaves RedNet's stream for the side graph
-        net._txt_last = True
-        # ... and with fewer than 8 images some XCDs stay free of it: the bi-LSTM's blocks that land there take all the work
-        # (ops.lstm_bidir spare) instead of half of them waiting for the depth encoder to end
+        # With fewer than 8 images some XCDs stay free of the persistent depth encoder: the bi-LSTM's blocks that land there
+        # take all the work (ops.lstm_bidir spare) instead of half of them waiting for the depth encoder to end
         ienc = net.instruction_encoder
         # (2B * spare blocks so that 2B of them land on the 8 - B free XCDs; measured at 4 and 5 images: 667 -> 620 us per
         #  step; at 6 and 7 - spare 4 and 8 - the recurrence still started only when the depth encoder ended: left alone)
         spare = int(os.environ.get("IVLN_LSTM_SPARE", str(2 if B <= 4 else 3 if B == 5 else 1)))
-        if net._txt_last and not predicted and spare > 1 and B < 8:
+        if step.txt_last and not predicted and spare > 1 and B < 8:
             # (the captured launches hold this word's ADDRESS: it lives as long as this object's graphs, whatever a later
             #  capture of the same policy hangs on the module)
             self._lstm_ticket = ienc.lstm_ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -324,8 +307,8 @@ class GraphedRollout:
         with self._dry_mapper():
             with torch.cuda.stream(s):  # warm-up: tables, workspaces (per stream), folded weights
                 for i in range(warmup):
-                    run_A()
-                    run_B2(i & 1, run_B1(i & 1))
+                    dep, txt = run_A()
+                    run_B2(i & 1, dep, *run_B1(i & 1, txt))
             if warmup:
                 # ... and once on the streams the graphs are captured on: per-stream state (split-K workspaces, GroupNorm /
                 # packed-weight scratch, the depth encoder's arena) must not be born inside a capture - a buffer from a
@@ -333,8 +316,8 @@ class GraphedRollout:
                 s.synchronize()
                 cap_stream.wait_stream(s)
                 with torch.cuda.stream(cap_stream):
-                    run_A()
-                    run_B2(0, run_B1(0))
+                    dep, txt = run_A()
+                    run_B2(0, dep, *run_B1(0, txt))
                 cap_stream.synchronize()
             with torch.cuda.stream(self.sA):  # the side stream needs its own split-K workspace before capture
                 run_A()
@@ -362,14 +345,13 @@ class GraphedRollout:
                     ca.cut()
             prev_hook, _rednet.STAGE_HOOK = _rednet.STAGE_HOOK, (hook_a if self._prefix else None)
             try:
-                run_A()
+                # (depth features, k/v) live in gA's pool - with predicted semantics the instruction features too
+                self._dep, self._txt = run_A()
             finally:
                 _rednet.STAGE_HOOK = prev_hook
         # [mapper prefix | depth encoder (+ instruction encoder)], or the one graph: a_tags names the boundary behind each piece but the last
         self.gA_parts, self._a_tags = list(ca.graphs), a_tags
         self.gA = self.gA_parts[-1]
-        self._dep = net._stash_dep  # (depth features, k/v) live in gA's pool
-        self._txt = getattr(net, "_stash_txt", None)  # (predicted semantics: the instruction features too)
         # the previous action (read by the embedding in gB1) ping-pongs with the state: one gB1 per phase
         self.ev_mid = torch.cuda.Event()
         self.gB1, pool = [], None
@@ -378,28 +360,25 @@ class GraphedRollout:
                 b_tags = []
 
                 def hook(name, cc=cc, b_tags=b_tags):
-                    if name == self._cut_stage and "mid" not in b_tags:
+                    if name == self._cut_at and "mid" not in b_tags:
                         b_tags.append("mid")
                         cc.cut()
                     elif name == "labels" and self._prefix and "labels" not in b_tags and "mid" in b_tags:
                         b_tags.append("labels")
                         cc.cut()  # (the mapper's second half starts here: the replay waits for the prefix's event in between)
-                prev_hook, _rednet.STAGE_HOOK = _rednet.STAGE_HOOK, (hook if self._cut_stage else None)
+                prev_hook, _rednet.STAGE_HOOK = _rednet.STAGE_HOOK, (hook if self._cut_at else None)
                 try:
-                    net._stash_txt = self._txt
-                    batch = run_B1(src)
+                    batch, pre = run_B1(src, self._txt)
                 finally:
                     _rednet.STAGE_HOOK = prev_hook
             pool = cc.pool
-            stash = net._stash
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, pool=pool, stream=cap_stream):
-                net._stash, net._stash_dep = stash, self._dep
-                run_B2(src, batch)
+                run_B2(src, self._dep, batch, pre)
             self.gB1.append(list(cc.graphs))
             self._b_tags = b_tags  # (the same cuts in both phases)
             self.graphs.append(g2)
-        self._keep = (batch, stash)
+        self._keep = (batch, pre)
         self.phase = 0
         if venc is not None:
             venc.beside_other_work = False  # (the captured launches are what they are; eager calls decide for themselves)
@@ -450,23 +429,18 @@ class GraphedRollout:
         main.wait_event(self.ev_A)
         self.graphs[self.phase].replay()
 
+    @contextlib.contextmanager
     def _dry_mapper(self):
         """Context: the transforms' mappers skip their own kernels (warmup_mapper=False), nothing otherwise."""
-        import contextlib
-
-        mms = [] if self._warmup_mapper else [mm for mm in (getattr(t, "mapping_module", None) for t in self.transforms) if mm is not None]
-
-        @contextlib.contextmanager
-        def ctx():
+        mods = (getattr(t, "mapping_module", None) for t in self.transforms)
+        mms = [] if self._warmup_mapper else [mm for mm in mods if mm is not None]
+        for mm in mms:
+            mm.dry_run = True
+        try:
+            yield
+        finally:
             for mm in mms:
-                mm.dry_run = True
-            try:
-                yield
-            finally:
-                for mm in mms:
-                    mm.dry_run = False
-
-        return ctx()
+                mm.dry_run = False
 
     def _capture(self, warmup):
         s = _stream(self.device, "warmup")
@@ -559,8 +533,7 @@ class GraphedRollout:
         channels of the depth branch's (B, 192, 4, 4) buffer in the side graph's pool."""
         if not self.split:
             return None
-        dep = self._dep[0]
-        return dep[:, : self.policy.net.depth_encoder.visual_encoder.output_shape[0]]
+        return self._dep[0][:, : self.policy.net.depth_encoder.visual_encoder.output_shape[0]]
 
     def reset_state(self):
         for t in self.rnn + self.prev:

@@ -5,6 +5,7 @@ no arithmetic itself; tensor allocation and views are the only torch operations 
 """
 import ctypes as C
 import contextlib
+import functools
 import os
 from typing import Optional
 
@@ -1102,8 +1103,27 @@ class CmaStepDesc(C.Structure):
 # rollout head: 0 = ivln_cma_step_fwd (folded operands, five phase kernels; ivln_cma_step_lstm_fwd for LSTM encoders),
 # -1 = the unfused chain of ten separate ops (A/B switch IVLN_CMA_STEP_MODE; measured 0.977 vs 0.988 ms per 4-env GRU step)
 CMA_STEP_MODE = int(os.environ.get("IVLN_CMA_STEP_MODE", "0"))
-_cma_ws = {}
+_cma_ws, _cma_lstm_ws = {}, {}  # scratch per form: nothing is shared between the GRU and the LSTM head
 CMA_WS_OWNER = 0  # graphed.GraphedRollout sets its own id while it warms up / captures: every runner owns a workspace
+
+
+@functools.lru_cache(maxsize=None)
+def _cma_L():
+    """The library, with the signatures of the four ivln_cma_step* entry points set (once: the result is cached)."""
+    L_ = _L()
+    L_.ivln_cma_step_ws_floats.restype = L_.ivln_cma_step_lstm_ws_floats.restype = i64
+    L_.ivln_cma_step_ws_floats.argtypes = L_.ivln_cma_step_lstm_ws_floats.argtypes = [i32, i32, i32, i32]
+    L_.ivln_cma_step_fwd.argtypes = L_.ivln_cma_step_lstm_fwd.argtypes = [C.POINTER(CmaStepDesc), i32, vp]
+    return L_
+
+
+def _cma_form_ws(name, floats, cache, rows, L, P, H, device):
+    key = (str(device), rows, L, P, H, CMA_WS_OWNER)
+    if key not in cache:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.IvlnError(name + " workspace must exist before stream capture (run one warm-up step first)")
+        cache[key] = torch.zeros(floats(rows, L, P, H), dtype=torch.float32, device=device)
+    return cache[key]
 
 
 def cma_step_ws(rows, L, P, H, device):
@@ -1113,18 +1133,7 @@ def cma_step_ws(rows, L, P, H, device):
     capturing GraphedRollout's id for a captured step (its pointer is baked into that graph).  Not keyed by stream:
     the buffer must not be born inside a stream capture (it would belong to that graph's private pool and outlive it
     in this cache) - the warm-up steps that precede every capture create it, on another stream than the capture."""
-    L_ = _L()
-    L_.ivln_cma_step_ws_floats.restype = i64
-    L_.ivln_cma_step_ws_floats.argtypes = [i32, i32, i32, i32]
-    n = L_.ivln_cma_step_ws_floats(rows, L, P, H)
-    key = (str(device), rows, L, P, H, CMA_WS_OWNER)
-    w = _cma_ws.get(key)
-    if w is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.IvlnError("cma_step workspace must exist before stream capture (run one warm-up step first)")
-        w = torch.zeros(n, dtype=torch.float32, device=device)
-        _cma_ws[key] = w
-    return w
+    return _cma_form_ws("cma_step", _cma_L().ivln_cma_step_ws_floats, _cma_ws, rows, L, P, H, device)
 
 
 def release_cma_ws(owner):
@@ -1134,39 +1143,20 @@ def release_cma_ws(owner):
 
 
 def cma_step(d: CmaStepDesc, mode=None):
-    L_ = _L()
-    L_.ivln_cma_step_fwd.argtypes = [C.POINTER(CmaStepDesc), i32, vp]
-    check(L_.ivln_cma_step_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_fwd")
+    check(_cma_L().ivln_cma_step_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_fwd")
 
 
-# the same head with LSTM state encoders (ivln_cma_step_lstm_fwd): its own entry point and its own scratch - nothing is
-# shared with the GRU form, whose launches and buffers stay what they are beside an LSTM policy in the same process.
-# CMA_STEP_MODE < 0 turns both forms off.
-_cma_lstm_ws = {}
-
-
+# the same head with LSTM state encoders (ivln_cma_step_lstm_fwd): its own entry point and its own scratch, so the GRU
+# form's launches and buffers stay what they are beside an LSTM policy in the same process.  CMA_STEP_MODE < 0: both off.
 def cma_step_lstm_ws(rows, L, P, H, device):
     """Scratch of the fused LSTM head, one per (device, shape, OWNER) as `cma_step_ws` keeps it for the GRU form (same
     ownership and capture rules); larger than that one by the rows x 4H hidden half of the second encoder."""
-    L_ = _L()
-    L_.ivln_cma_step_lstm_ws_floats.restype = i64
-    L_.ivln_cma_step_lstm_ws_floats.argtypes = [i32, i32, i32, i32]
-    n = L_.ivln_cma_step_lstm_ws_floats(rows, L, P, H)
-    key = (str(device), rows, L, P, H, CMA_WS_OWNER)
-    w = _cma_lstm_ws.get(key)
-    if w is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.IvlnError("cma_step_lstm workspace must exist before stream capture (run one warm-up step first)")
-        w = torch.zeros(n, dtype=torch.float32, device=device)
-        _cma_lstm_ws[key] = w
-    return w
+    return _cma_form_ws("cma_step_lstm", _cma_L().ivln_cma_step_lstm_ws_floats, _cma_lstm_ws, rows, L, P, H, device)
 
 
 def cma_step_lstm(d: CmaStepDesc, mode=None):
     """`d` read the LSTM way (include/ivln_hip.h): 4H weight rows, h_in / h_out (rows, 4, H) views [h1 | c1 | h2 | c2]."""
-    L_ = _L()
-    L_.ivln_cma_step_lstm_fwd.argtypes = [C.POINTER(CmaStepDesc), i32, vp]
-    check(L_.ivln_cma_step_lstm_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_lstm_fwd")
+    check(_cma_L().ivln_cma_step_lstm_fwd(C.byref(d), 0, stream_ptr()), "ivln_cma_step_lstm_fwd")
 
 
 WEIGHT_EPOCH = 0  # bumped by FlatAdam.step(): kernels update parameters through raw pointers, which

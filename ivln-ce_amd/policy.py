@@ -7,6 +7,7 @@ torch.nn modules hold parameters only.  The whole net forward is one torch.autog
 backward runs the hand-written HIP backward kernels (train.py), so `loss.backward()` in a trainer
 (base_il_trainer.py:211) works unchanged.
 """
+from collections import namedtuple
 from typing import Tuple
 
 import numpy as np
@@ -66,6 +67,23 @@ class CategoricalNet(nn.Module):
 
     def forward(self, x: Tensor) -> CustomFixedCategorical:
         return CustomFixedCategorical(logits=self.raw_logits(x))
+
+
+class StepGeometry(namedtuple("StepGeometry", "d_out m_out E x2w o_txt o_dep o_map o_prev")):
+    """Column layout of the two row buffers of a MapCMANet step: state_in = [dep_in | map_in | prev] (d_out, m_out, E
+    wide), x2 = [state | text | dep' | map' | prev] (x2w wide; text / dep' / map' / prev begin at the four offsets)."""
+
+    def buffers(self, rows, device):
+        """-> (state_in, x2) for `rows` rows."""
+        return (torch.empty((rows, self.d_out + self.m_out + self.E), dtype=torch.float32, device=device),
+                torch.empty((rows, self.x2w), dtype=torch.float32, device=device))
+
+
+# What one graphed.GraphedRollout in split mode shares between MapCMANet's three stages: the persistent row buffers, and
+# where the instruction branch runs - in the depth stage behind (txt_with_dep True) or in front of ("first") the depth
+# encoder, else in the pre stage, as its last branch (txt_last) or its first.  ("first" is a measurement variant kept from
+# the 8-image experiments: no caller in the repository passes it.)
+SplitStep = namedtuple("SplitStep", "state_in x2 txt_with_dep txt_last", defaults=(False, False))
 
 
 class MapCMANet(Net):
@@ -204,232 +222,160 @@ class MapCMANet(Net):
             self._cma_fold_key, self._cma_fold = key, (wf, bf)
         return self._cma_fold
 
+    @staticmethod
+    def _fused_head_ops(form):
+        """(scratch, entry point) of a fused head form in `ops`; None for the unfused chain."""
+        return {"gru": (ops.cma_step_ws, ops.cma_step), "lstm": (ops.cma_step_lstm_ws, ops.cma_step_lstm)}.get(form)
+
     def prepare_capture(self, example_obs):
         """Create everything the rollout step caches lazily BEFORE a stream capture (graphed.py): a buffer born inside
         a capture lives in that graph's private pool and must not survive in a process-wide cache."""
-        form = self.fused_head_form
-        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or form is None:
+        head = self._fused_head_ops(self.fused_head_form)
+        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or head is None:
             return
         rows, L = example_obs["instruction"].shape[0], example_obs["instruction"].shape[1]
         P = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         if P > 16 or L > 512:
-            return  # outside the fused head's envelope: forward_hip takes the unfused chain
+            return  # outside the fused head's envelope: the step takes the unfused chain
         self._cma_fold_weights()
-        ws = ops.cma_step_lstm_ws if form == "lstm" else ops.cma_step_ws
-        ws(rows, L, P, self._hidden_size, example_obs["instruction"].device)
+        head[0](rows, L, P, self._hidden_size, example_obs["instruction"].device)
 
     def _init_layers(self):
         if self.model_config.PROGRESS_MONITOR.use:
             nn.init.kaiming_normal_(self.progress_monitor.weight, nonlinearity="tanh")
             nn.init.constant_(self.progress_monitor.bias, 0)
 
-    # ------------------------------------------------------------------------------------------
-    def forward_hip(self, observations, rnn_states, prev_actions, action_masks, save=None):
-        """HIP forward of map_cma_policy.py:276-353.  Returns (features (rows,512), rnn_states_out
-        (N, num_recurrent_layers, H)).  `save` (dict) collects what the HIP backward needs."""
-        mc = self.model_config
-        dev = rnn_states.device
-        H = self._hidden_size
-        h2 = H // 2
-        N = rnn_states.shape[0]
-        rnn_states = rnn_states.to(torch.float32).contiguous()
-        masks_u8 = action_masks.reshape(-1).to(torch.uint8).contiguous()
-        rows = masks_u8.shape[0]
-        prev_actions = prev_actions.reshape(-1).long().contiguous()
+    # ---- the parts of one step ----------------------------------------------------------------
+    @property
+    def step_geometry(self):
+        d_out, m_out = self.depth_linear[1].out_features, self.map_linear[1].out_features
+        E, o_txt = self.prev_action_embedding.embedding_dim, self._hidden_size
+        o_dep = o_txt + self.instruction_encoder.output_size
+        o_map, o_prev = o_dep + d_out, o_dep + d_out + m_out
+        return StepGeometry(d_out, m_out, E, o_prev + E, o_txt, o_dep, o_map, o_prev)
 
-        s_txt = {} if save is not None else None
-        s_map = [] if save is not None else None
-        d_out = self.depth_linear[1].out_features
-        m_out = self.map_linear[1].out_features
-        E = self.prev_action_embedding.embedding_dim
-        # state_in = [dep_in | map_in | prev]; x2 = [state | text | dep' | map' | prev]
-        x2w = H + self.instruction_encoder.output_size + d_out + m_out + E
-        persist = getattr(self, "_persist", None) if save is None else None  # graphed.py split mode
-        if persist is not None and persist["state_in"].shape[0] == rows:
-            state_in, x2 = persist["state_in"], persist["x2"]
-        else:
-            state_in = torch.empty((rows, d_out + m_out + E), dtype=torch.float32, device=dev)
-            x2 = torch.empty((rows, x2w), dtype=torch.float32, device=dev)
-        dl, ml = self.depth_linear[1], self.map_linear[1]
-        o_txt, o_dep, o_map, o_prev = H, H + 256, H + 256 + d_out, H + 256 + d_out + m_out
+    @staticmethod
+    def _step_inputs(rnn_states, prev_actions, action_masks):
+        """The step's inputs as the kernels take them: float32 states, (rows,) uint8 masks, (rows,) int64 actions."""
+        return (rnn_states.to(torch.float32).contiguous(), action_masks.reshape(-1).to(torch.uint8).contiguous(),
+                prev_actions.reshape(-1).long().contiguous())
 
-        # The fused recurrent head (ivln_cma_step_fwd; ivln_cma_step_lstm_fwd with LSTM encoders - the fold does not depend
-        # on the cell) wants the instruction branch to emit the folded [Mq | TQb] operand instead of text_k, so its
-        # eligibility is decided HERE, from shapes known before any branch runs (the encoders' static output shapes, the
-        # token axis, the widths' divisibility rules of csrc/cma_step.hip) - anything outside the kernel's envelope
-        # takes the unfused chain with a real text_k.
+    def _fused_head_eligible(self, observations, save):
+        """The fused recurrent head (ivln_cma_step_fwd; ivln_cma_step_lstm_fwd with LSTM encoders - the fold does not
+        depend on the cell) wants the instruction branch to emit the folded [Mq | TQb] operand instead of text_k, so its
+        eligibility is decided from shapes known before any branch runs (the encoders' static output shapes, the token
+        axis, the widths' divisibility rules of csrc/cma_step.hip) - anything outside the kernel's envelope takes the
+        unfused chain with a real text_k."""
+        mc, geo = self.model_config, self.step_geometry
+        H, h2 = self._hidden_size, self._hidden_size // 2
         P_static = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         L_static = observations["instruction"].shape[-1] if "instruction" in observations else 0
-        head_form = self.fused_head_form
-        fused_head = (save is None and ops.CMA_STEP_MODE >= 0 and head_form is not None
-                      and not (mc.ablate_instruction or mc.ablate_depth or mc.ablate_map)
-                      and P_static <= 16 and 0 < L_static <= 512
-                      and self.map_encoder.output_shape[1] * self.map_encoder.output_shape[2] == P_static
-                      and H % 64 == 0 and h2 % 64 == 0 and d_out % 16 == 0 and m_out % 16 == 0
-                      and self.instruction_encoder.output_size % 64 == 0)
+        return (save is None and ops.CMA_STEP_MODE >= 0 and self.fused_head_form is not None
+                and not (mc.ablate_instruction or mc.ablate_depth or mc.ablate_map)
+                and P_static <= 16 and 0 < L_static <= 512
+                and self.map_encoder.output_shape[1] * self.map_encoder.output_shape[2] == P_static
+                and H % 64 == 0 and h2 % 64 == 0 and geo.d_out % 16 == 0 and geo.m_out % 16 == 0
+                and self.instruction_encoder.output_size % 64 == 0)
 
-        # update batches: the instruction of a trajectory is the same at every timestep, so the loader hands over the
-        # UNIQUE token rows and each row's index into them (trainers.PrefetchLoader); the encoder, text_k and their
-        # backward then run on U sequences instead of T*N (8-9 instead of 512 at the benched shape)
-        inv = None
-        if save is not None and "instruction_index" in observations and "instruction_unique" in observations:
-            inv = observations["instruction_index"].reshape(-1).to(torch.int32).contiguous()
-
-        def _txt_branch(sv):
-            src = observations if inv is None else {"instruction": observations["instruction_unique"]}
-            t, ln = self.instruction_encoder(src, sv)  # (rows | U, 256, L)
-            if mc.ablate_instruction:
-                t = torch.zeros_like(t)
-            r_, L_ = t.shape[0], t.shape[2]
-            if fused_head:
-                # rollout: text_k, state_q and text_q folded over the instruction (csrc/cma_step.hip): ONE 1x1 conv
-                # yields Mq (H+1 channels) and TQb (h2 channels) for the fused head, no text_k tensor is made
-                wf, bf = self._cma_fold_weights()
-                cache = self.instruction_encoder.last_cache if sv is None else None
-                if cache is not None and getattr(cache, "fold_behind", False):
-                    # an earlier cached call re-encoded rows without folding them (the unfused head, or a capture that had
-                    # to drop the cache): `dirty` only names THIS call's rows, so every row is folded again (ADVICE r5)
+    def _txt_branch(self, observations, fused_head, sv, inv=None):
+        """Instruction encoder + what the head reads the instruction through: -> (txt (rows | U, 256, L), lengths, tk),
+        tk = text_k's keys, or the folded [Mq | TQb] operand when `fused_head`.  `inv`: see forward_hip."""
+        mc, h2 = self.model_config, self._hidden_size // 2
+        src = observations if inv is None else {"instruction": observations["instruction_unique"]}
+        t, ln = self.instruction_encoder(src, sv)  # (rows | U, 256, L)
+        if mc.ablate_instruction:
+            t = torch.zeros_like(t)
+        r_, L_ = t.shape[0], t.shape[2]
+        if fused_head:
+            # rollout: text_k, state_q and text_q folded over the instruction (csrc/cma_step.hip): ONE 1x1 conv
+            # yields Mq (H+1 channels) and TQb (h2 channels) for the fused head, no text_k tensor is made
+            wf, bf = self._cma_fold_weights()
+            cache = self.instruction_encoder.last_cache if sv is None else None
+            if cache is not None and getattr(cache, "fold_behind", False):
+                # an earlier cached call re-encoded rows without folding them (the unfused head, or a capture that had
+                # to drop the cache): `dirty` only names THIS call's rows, so every row is folded again (ADVICE r5)
+                if torch.cuda.is_current_stream_capturing():
+                    cache = None
+                else:
+                    cache.dirty.fill_(1)
+                    cache.fold_behind = False
+            if cache is not None:
+                # per-episode cache (encoders.InstructionEncoder.step_cache): the folded operands live in the cache's
+                # persistent buffer and only the rows the encoder just re-encoded (cache.dirty) are recomputed
+                fkey = getattr(self, "_cma_fold_key", None)
+                if cache.fold is None or cache.fold_key != fkey:
                     if torch.cuda.is_current_stream_capturing():
-                        cache = None
+                        cache.fold_behind = True  # (the replays advance the cache's tokens without its fold)
+                        cache = None  # (cannot be created / invalidated inside a capture: plain conv below)
                     else:
-                        cache.dirty.fill_(1)
-                        cache.fold_behind = False
-                if cache is not None:
-                    # per-episode cache (encoders.InstructionEncoder.step_cache): the folded operands live in the cache's
-                    # persistent buffer and only the rows the encoder just re-encoded (cache.dirty) are recomputed
-                    fkey = getattr(self, "_cma_fold_key", None)
-                    if cache.fold is None or cache.fold_key != fkey:
-                        if torch.cuda.is_current_stream_capturing():
-                            cache.fold_behind = True  # (the replays advance the cache's tokens without its fold)
-                            cache = None  # (cannot be created / invalidated inside a capture: plain conv below)
-                        else:
-                            if cache.fold is None:
-                                cache.fold = torch.zeros((r_, wf.shape[0], 1, L_), dtype=torch.float32, device=t.device)
-                            cache.fold_key = fkey
-                            cache.dirty.fill_(1)  # (folded for other weights, or never: every row's operands are made now)
-                if cache is not None:
-                    ops.conv2d(t.view(r_, -1, 1, L_), wf.view(wf.shape[0], -1, 1, 1), shift=bf, splitk=False, out=cache.fold,
-                               run_flags=cache.dirty)
-                    return t, ln, cache.fold.view(r_, -1, L_)
-                # (no cache: every row is "dirty" - the same kernel as the cached call, so that the two agree bit for bit
-                #  whatever the tile heuristics make of a plain 1x1 conv of this shape)
-                fold = ops.conv2d(t.view(r_, -1, 1, L_), wf.view(wf.shape[0], -1, 1, 1), shift=bf, splitk=False,
-                                  run_flags=ops.all_rows_flags(r_, t.device))
-                return t, ln, fold.view(r_, -1, L_)
-            if sv is None and self.instruction_encoder.last_cache is not None:
-                self.instruction_encoder.last_cache.fold_behind = True  # (cached encoding, no fold made for its dirty rows)
-            tk_ = ops.conv2d(t.view(r_, -1, 1, L_), self.text_k.weight.view(h2, -1, 1, 1), shift=self.text_k.bias,
-                             splitk=False)
-            return t, ln, tk_
+                        if cache.fold is None:
+                            cache.fold = torch.zeros((r_, wf.shape[0], 1, L_), dtype=torch.float32, device=t.device)
+                        cache.fold_key = fkey
+                        cache.dirty.fill_(1)  # (folded for other weights, or never: every row's operands are made now)
+            if cache is not None:
+                ops.conv2d(t.view(r_, -1, 1, L_), wf.view(wf.shape[0], -1, 1, 1), shift=bf, splitk=False, out=cache.fold,
+                           run_flags=cache.dirty)
+                return t, ln, cache.fold.view(r_, -1, L_)
+            # (no cache: every row is "dirty" - the same kernel as the cached call, so that the two agree bit for bit
+            #  whatever the tile heuristics make of a plain 1x1 conv of this shape)
+            fold = ops.conv2d(t.view(r_, -1, 1, L_), wf.view(wf.shape[0], -1, 1, 1), shift=bf, splitk=False,
+                              run_flags=ops.all_rows_flags(r_, t.device))
+            return t, ln, fold.view(r_, -1, L_)
+        if sv is None and self.instruction_encoder.last_cache is not None:
+            self.instruction_encoder.last_cache.fold_behind = True  # (cached encoding, no fold made for its dirty rows)
+        tk_ = ops.conv2d(t.view(r_, -1, 1, L_), self.text_k.weight.view(h2, -1, 1, 1), shift=self.text_k.bias,
+                         splitk=False)
+        return t, ln, tk_
 
-        def _map_branch(sv):
-            m = self.map_encoder(observations, sv)  # (rows,128,4,4)
-            if mc.ablate_map:
-                m = torch.zeros_like(m)
-            r_, Cm_, P_ = m.shape[0], m.shape[1], m.shape[2] * m.shape[3]
-            # k/v projection + map_linear: one launch for rollout batches, else the MFMA GEMM + the skinny linear
-            kv = ops.kv_linear(m, self.map_kv.weight, self.map_kv.bias, ml.weight, ml.bias, state_in[:, d_out:d_out + m_out])
-            if kv is None:
-                kv = ops.conv2d(m.view(r_, Cm_, 1, P_), self.map_kv.weight.view(-1, Cm_, 1, 1), shift=self.map_kv.bias,
-                                splitk=False)
-                ops.linear(m.view(r_, -1), ml.weight, ml.bias, relu=True, out=state_in[:, d_out:d_out + m_out])
-            return m, kv
+    def _kv_branch(self, x, kv_conv, lin, out):
+        """An image branch's tail: the k/v projection of the features x (rows, C, h, w) -> returned, and `lin` + ReLU of
+        them -> `out` (a column block of state_in).  The projections depend only on their own encoder, so they run
+        inside the branches: one launch for rollout batches, else the MFMA GEMM + the skinny linear."""
+        r_, C_, P_ = x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
+        kv = ops.kv_linear(x, kv_conv.weight, kv_conv.bias, lin.weight, lin.bias, out)
+        if kv is None:
+            kv = ops.conv2d(x.view(r_, C_, 1, P_), kv_conv.weight.view(-1, C_, 1, 1), shift=kv_conv.bias, splitk=False)
+            ops.linear(x.view(r_, -1), lin.weight, lin.bias, relu=True, out=out)
+        return kv
 
-        def _dep_branch():
-            d = self.depth_encoder(observations)  # (rows,192,4,4)
-            if mc.ablate_depth:
-                d = torch.zeros_like(d)
-            r_, Cd_, P_ = d.shape[0], d.shape[1], d.shape[2] * d.shape[3]
-            kv = ops.kv_linear(d, self.dep_kv.weight, self.dep_kv.bias, dl.weight, dl.bias, state_in[:, :d_out])
-            if kv is None:
-                kv = ops.conv2d(d.view(r_, Cd_, 1, P_), self.dep_kv.weight.view(-1, Cd_, 1, 1), shift=self.dep_kv.bias,
-                                splitk=False)
-                ops.linear(d.view(r_, -1), dl.weight, dl.bias, relu=True, out=state_in[:, :d_out])
-            return d, kv
+    def _map_branch(self, observations, state_in, sv):
+        """Semantic-map CNN -> (features (rows,128,4,4), k/v); map_linear fills its columns of state_in."""
+        geo = self.step_geometry
+        m = self.map_encoder(observations, sv)
+        if self.model_config.ablate_map:
+            m = torch.zeros_like(m)
+        return m, self._kv_branch(m, self.map_kv, self.map_linear[1], state_in[:, geo.d_out:geo.d_out + geo.m_out])
 
-        # The key/value projections depend only on their own encoder, so they run inside the branches.
-        side = getattr(self, "_side_streams", None) if save is None else None
-        stage = getattr(self, "_stage", None) if save is None else None
-        if stage == "dep":
-            # graphed.py, split mode: depth ResNet + its k/v projection + depth_linear as one graph on a side
-            # stream (they depend on nothing but the new depth image); results land in the persistent buffers
-            if getattr(self, "_txt_with_dep", False) == "first":
-                # 8 images: the persistent depth encoder leaves no XCD for the bi-LSTM, which then runs in front of it
-                self._stash_txt = _txt_branch(None)
-            self._stash_dep = _dep_branch()
-            if getattr(self, "_txt_with_dep", False) is True:
-                # predicted semantics: the main stream is RedNet's critical path, the instruction encoder moves here
-                self._stash_txt = _txt_branch(None)
-            return None, None
-        if stage == "pre":
-            # ... while the instruction and map branches (and the previous-action embedding) run as a second
-            # graph on the main stream
-            # (order: when the persistent depth encoder is the neighbour, the bi-LSTM - 340 registers per SIMD lane - cannot
-            #  be scheduled before that launch ends; last in this graph it delays nothing else - graphed.py sets _txt_last)
-            last = getattr(self, "_txt_last", False) and not getattr(self, "_txt_with_dep", False)
-            if not last:
-                txt, lengths, tk = self._stash_txt if getattr(self, "_txt_with_dep", False) else _txt_branch(None)
-            mp, mkv = _map_branch(None)
-            if last:
-                txt, lengths, tk = _txt_branch(None)
-            ops.prev_action_embed(prev_actions, masks_u8, self.prev_action_embedding.weight,
-                                  state_in[:, d_out + m_out:], x2[:, o_prev:])
-            self._stash = dict(txt=(txt, lengths, tk), map=(mp, mkv))
-            return None, None
-        if stage == "post":
-            st = self._stash
-            txt, lengths, tk = st["txt"]
-            mp, mkv = st["map"]
-            dep, dkv = self._stash_dep
-        elif side is None:
-            from . import train as _train
+    def _dep_branch(self, observations, state_in):
+        """Depth ResNet -> (features (rows,192,4,4), k/v); depth_linear fills its columns of state_in."""
+        d = self.depth_encoder(observations)
+        if self.model_config.ablate_depth:
+            d = torch.zeros_like(d)
+        return d, self._kv_branch(d, self.dep_kv, self.depth_linear[1], state_in[:, :self.step_geometry.d_out])
 
-            overlap = save is not None and _train.OVERLAP_INSTRUCTION and not torch.cuda.is_current_stream_capturing()
-            if overlap:  # training pass: the instruction bi-LSTM runs beside the map CNN (train.py)
-                cur, st = torch.cuda.current_stream(), _train.side_stream(dev)
-                st.wait_stream(cur)
-                _train.share_with_stream((observations.get("instruction"), observations.get("instruction_unique")), st)
-                with torch.cuda.stream(st):
-                    txt, lengths, tk = _txt_branch(s_txt)
-            else:
-                txt, lengths, tk = _txt_branch(s_txt)
-            dep, dkv = _dep_branch()
-            mp, mkv = _map_branch(s_map)
-            if overlap:
-                cur.wait_stream(st)
-                _train.share_with_stream((txt, lengths, tk, s_txt), cur)
-        else:
-            # three independent, latency-bound branches on forked streams (graphed.py): depth ResNet
-            # (critical path, submitted first) || instruction bi-LSTM || (mapper ->) map CNN
-            cur = torch.cuda.current_stream()
-            st_txt, st_map = side
-            st_txt.wait_stream(cur)
-            st_map.wait_stream(cur)
-            dep, dkv = _dep_branch()
-            with torch.cuda.stream(st_txt):
-                txt, lengths, tk = _txt_branch(None)
-            with torch.cuda.stream(st_map):
-                mp, mkv = _map_branch(None)
-            cur.wait_stream(st_txt)
-            cur.wait_stream(st_map)
-        L = txt.shape[2]
-        Cd, Cm = dep.shape[1], mp.shape[1]
-        P = dep.shape[2] * dep.shape[3]
-        if stage != "post":
-            ops.prev_action_embed(prev_actions, masks_u8, self.prev_action_embedding.weight,
-                                  state_in[:, d_out + m_out:], x2[:, o_prev:])
+    def _prev_embed(self, prev_actions, masks_u8, state_in, x2):
+        geo = self.step_geometry
+        ops.prev_action_embed(prev_actions, masks_u8, self.prev_action_embedding.weight,
+                              state_in[:, geo.d_out + geo.m_out:], x2[:, geo.o_prev:])
 
-        rnn_out = getattr(self, "_rnn_out_buffer", None) if save is None else None  # graphed.py: persistent buffer
-        if rnn_out is None:
-            rnn_out = torch.empty_like(rnn_states)
+    def _head(self, rnn_states, masks_u8, state_in, x2, txt3, dep2, map2, fused_head, rnn_out=None, save=None, inv=None):
+        """Recurrent / attention head over the three branches' results txt3 = (txt, lengths, tk), dep2 = (dep, dkv),
+        map2 = (mp, mkv) -> (features (rows, H), rnn_out).  `rnn_out`: where the new states go (graphed.py: a persistent
+        buffer).  The unfused chain leaves what the HIP backward needs of it in `save`."""
+        (txt, lengths, tk), (dep, dkv), (mp, mkv) = txt3, dep2, map2
+        geo, dev = self.step_geometry, rnn_states.device
+        H, h2, rows = self._hidden_size, self._hidden_size // 2, masks_u8.shape[0]
+        L, P = txt.shape[2], dep.shape[2] * dep.shape[3]
+        rnn_out = torch.empty_like(rnn_states) if rnn_out is None else rnn_out
+        feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
         if fused_head and P <= 16 and L <= 512 and tk.shape[1] == H + 1 + h2:
             # GRU-1 -> text attention -> depth / map attention -> compress -> GRU-2 as one C-ABI call (five phase kernels,
             # csrc/cma_step.hip); `tk` holds the folded [Mq | TQb] operand here.  With LSTM encoders the same descriptor
             # goes to the LSTM form: 4H weight rows, and the (rows, 4, H) states [h1 | c1 | h2 | c2]
-            feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
             g1, g2, sc = self.state_encoder.rnn, self.second_state_encoder.rnn, self.second_state_compress[0]
             d = ops.CmaStepDesc()
-            d.rows, d.L, d.P, d.H, d.Hq, d.Ct, d.d_out, d.m_out, d.E, d.x2w = rows, L, P, H, h2, txt.shape[1], d_out, m_out, E, x2w
+            d.rows, d.L, d.P, d.H, d.Hq, d.Ct = rows, L, P, H, h2, txt.shape[1]
+            d.d_out, d.m_out, d.E, d.x2w = geo.d_out, geo.m_out, geo.E, geo.x2w
             d.state_in, d.h_in, d.ld_h, d.mask = ops.dptr(state_in), ops.dptr(rnn_states), rnn_states.stride(0), ops.dptr(masks_u8)
             d.w_ih1, d.w_hh1, d.b_ih1, d.b_hh1 = (ops.dptr(g1.weight_ih_l0), ops.dptr(g1.weight_hh_l0),
                                                   ops.dptr(g1.bias_ih_l0), ops.dptr(g1.bias_hh_l0))
@@ -441,16 +387,11 @@ class MapCMANet(Net):
             d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2 = (ops.dptr(g2.weight_ih_l0), ops.dptr(g2.weight_hh_l0),
                                                   ops.dptr(g2.bias_ih_l0), ops.dptr(g2.bias_hh_l0))
             d.x2, d.h_out, d.ld_ho, d.feats = ops.dptr(x2), ops.dptr(rnn_out), rnn_out.stride(0), ops.dptr(feats)
-            if head_form == "lstm":
-                d.ws = ops.dptr(ops.cma_step_lstm_ws(rows, L, P, H, dev))
-                ops.cma_step_lstm(d)
-            else:
-                ws = ops.cma_step_ws(rows, L, P, H, dev)
-                d.ws = ops.dptr(ws)
-                ops.cma_step(d)
+            scratch, step = self._fused_head_ops(self.fused_head_form)
+            d.ws = ops.dptr(scratch(rows, L, P, H, dev))
+            step(d)
             return feats, rnn_out
-        s_g1 = {} if save is not None else None
-        s_g2 = {} if save is not None else None
+        s_g1, s_g2 = ({}, {}) if save is not None else (None, None)
         state = x2[:, :H]
         n1, n2 = self.state_encoder.num_recurrent_layers, self.second_state_encoder.num_recurrent_layers
         self.state_encoder(state_in, self._state_slot(rnn_states, 0, n1), masks_u8, state,
@@ -458,36 +399,133 @@ class MapCMANet(Net):
 
         q1 = ops.linear(state, self.state_q.weight, self.state_q.bias)
         a_txt = torch.empty((rows, L), dtype=torch.float32, device=dev) if save is not None else None
-        text = x2[:, o_txt:o_txt + 256]
+        text = x2[:, geo.o_txt:geo.o_dep]
         ops.attn(q1, tk.view(tk.shape[0], h2, L), txt, lengths, self._scale_f, text, a_txt, row_index=inv)
 
         dkv, mkv = dkv.view(rows, -1, P), mkv.view(rows, -1, P)
         q2 = ops.linear(text, self.text_q.weight, self.text_q.bias)
         a_dep = torch.empty((rows, P), dtype=torch.float32, device=dev) if save is not None else None
         a_map = torch.empty((rows, P), dtype=torch.float32, device=dev) if save is not None else None
+        x2_dep, x2_map = x2[:, geo.o_dep:geo.o_map], x2[:, geo.o_map:geo.o_prev]
         if save is None and P <= 32:
             # rollout head: both short-axis attentions (they share the query) in one launch
-            ops.attn_small2(q2, dkv[:, :h2], dkv[:, h2:], x2[:, o_dep:o_dep + d_out], mkv[:, :h2], mkv[:, h2:],
-                            x2[:, o_map:o_map + m_out], self._scale_f)
+            ops.attn_small2(q2, dkv[:, :h2], dkv[:, h2:], x2_dep, mkv[:, :h2], mkv[:, h2:], x2_map, self._scale_f)
         else:
-            ops.attn(q2, dkv[:, :h2], dkv[:, h2:], None, self._scale_f, x2[:, o_dep:o_dep + d_out], a_dep)
-            ops.attn(q2, mkv[:, :h2], mkv[:, h2:], None, self._scale_f, x2[:, o_map:o_map + m_out], a_map)
+            ops.attn(q2, dkv[:, :h2], dkv[:, h2:], None, self._scale_f, x2_dep, a_dep)
+            ops.attn(q2, mkv[:, :h2], mkv[:, h2:], None, self._scale_f, x2_map, a_map)
 
         sc = self.second_state_compress[0]
         c2 = ops.linear(x2, sc.weight, sc.bias, relu=True)
-        feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
         self.second_state_encoder(c2, self._state_slot(rnn_states, n1, n2), masks_u8, feats,
                                   self._state_slot(rnn_out, n1, n2), s_g2)
 
         if save is not None:
             save.update(
-                txt=s_txt, map=s_map, g1=s_g1, g2=s_g2, dep=dep, mp=mp, txt_out=txt, lengths=lengths,
+                g1=s_g1, g2=s_g2, dep=dep, mp=mp, txt_out=txt, lengths=lengths,
                 state_in=state_in, x2=x2, q1=q1, tk=tk, a_txt=a_txt, dkv=dkv, mkv=mkv, q2=q2, a_dep=a_dep,
-                a_map=a_map, c2=c2, feats=feats, rows=rows, N=N, L=L, P=P, offs=(o_txt, o_dep, o_map, o_prev),
-                masks=masks_u8, prev_actions=prev_actions, depth_from_features="depth_features" in observations,
-                inv=inv,
+                a_map=a_map, c2=c2, feats=feats, rows=rows, L=L, P=P,
+                offs=(geo.o_txt, geo.o_dep, geo.o_map, geo.o_prev), masks=masks_u8, inv=inv,
             )
         return feats, rnn_out
+
+    # ------------------------------------------------------------------------------------------
+    def forward_hip(self, observations, rnn_states, prev_actions, action_masks, save=None, *, side_streams=None,
+                    rnn_out=None):
+        """HIP forward of map_cma_policy.py:276-353.  Returns (features (rows,512), rnn_states_out
+        (N, num_recurrent_layers, H)).  `save` (dict) collects what the HIP backward needs.  A captured rollout step
+        (graphed.py) may name two `side_streams` to fork the instruction and map branches onto, and the buffer
+        `rnn_out` the new states are written to."""
+        dev = rnn_states.device
+        rnn_states, masks_u8, prev_actions = self._step_inputs(rnn_states, prev_actions, action_masks)
+        state_in, x2 = self.step_geometry.buffers(masks_u8.shape[0], dev)
+        fused_head = self._fused_head_eligible(observations, save)
+        s_txt, s_map = ({}, []) if save is not None else (None, None)
+
+        # update batches: the instruction of a trajectory is the same at every timestep, so the loader hands over the
+        # UNIQUE token rows and each row's index into them (trainers.PrefetchLoader); the encoder, text_k and their
+        # backward then run on U sequences instead of T*N (8-9 instead of 512 at the benched shape)
+        inv = None
+        if save is not None and "instruction_index" in observations and "instruction_unique" in observations:
+            inv = observations["instruction_index"].reshape(-1).to(torch.int32).contiguous()
+
+        if side_streams is None:
+            from . import train as _train
+
+            overlap = save is not None and _train.OVERLAP_INSTRUCTION and not torch.cuda.is_current_stream_capturing()
+            if overlap:  # training pass: the instruction bi-LSTM runs beside the map CNN (train.py)
+                cur, st = torch.cuda.current_stream(), _train.side_stream(dev)
+                st.wait_stream(cur)
+                _train.share_with_stream((observations.get("instruction"), observations.get("instruction_unique")), st)
+                with torch.cuda.stream(st):
+                    txt3 = self._txt_branch(observations, fused_head, s_txt, inv)
+            else:
+                txt3 = self._txt_branch(observations, fused_head, s_txt, inv)
+            dep2 = self._dep_branch(observations, state_in)
+            map2 = self._map_branch(observations, state_in, s_map)
+            if overlap:
+                cur.wait_stream(st)
+                _train.share_with_stream((*txt3, s_txt), cur)
+        else:
+            # three independent, latency-bound branches on forked streams (graphed.py): depth ResNet
+            # (critical path, submitted first) || instruction bi-LSTM || (mapper ->) map CNN
+            cur = torch.cuda.current_stream()
+            st_txt, st_map = side_streams
+            st_txt.wait_stream(cur)
+            st_map.wait_stream(cur)
+            dep2 = self._dep_branch(observations, state_in)
+            with torch.cuda.stream(st_txt):
+                txt3 = self._txt_branch(observations, fused_head, None)
+            with torch.cuda.stream(st_map):
+                map2 = self._map_branch(observations, state_in, None)
+            cur.wait_stream(st_txt)
+            cur.wait_stream(st_map)
+        self._prev_embed(prev_actions, masks_u8, state_in, x2)
+        feats, rnn_out = self._head(rnn_states, masks_u8, state_in, x2, txt3, dep2, map2, fused_head, rnn_out, save, inv)
+        if save is not None:
+            save.update(txt=s_txt, map=s_map, N=rnn_states.shape[0], prev_actions=prev_actions,
+                        depth_from_features="depth_features" in observations)
+        return feats, rnn_out
+
+    # ---- the same step as the three graphs of graphed.GraphedRollout's split mode: `step` is the runner's SplitStep, and
+    #      what a stage returns lives in its graph's pool - the runner keeps it and hands it to the next stage
+    def stage_depth(self, observations, rnn_states, prev_actions, action_masks, step):
+        """Depth ResNet + its k/v projection + depth_linear as one graph on a side stream (they depend on nothing but
+        the new depth image); results land in the persistent buffers.  -> (dep2, txt3 or None)."""
+        # (every stage converts the step's inputs, used or not: the conversions are launches, kept so that the three graphs
+        #  stay launch for launch what they were - dropping the unused ones changes the graphs: a measured follow-up)
+        self._step_inputs(rnn_states, prev_actions, action_masks)
+        fused_head = self._fused_head_eligible(observations, None)
+        txt3 = None
+        if step.txt_with_dep == "first":
+            # 8 images: the persistent depth encoder leaves no XCD for the bi-LSTM, which then runs in front of it
+            txt3 = self._txt_branch(observations, fused_head, None)
+        dep2 = self._dep_branch(observations, step.state_in)
+        if step.txt_with_dep is True:
+            # predicted semantics: the main stream is RedNet's critical path, the instruction encoder moves here
+            txt3 = self._txt_branch(observations, fused_head, None)
+        return dep2, txt3
+
+    def stage_pre(self, observations, rnn_states, prev_actions, action_masks, step, txt3=None):
+        """... while the instruction and map branches (and the previous-action embedding) run as a second graph on
+        the main stream.  `txt3`: the instruction branch's result when stage_depth ran it.  -> (txt3, map2)."""
+        _, masks_u8, prev_actions = self._step_inputs(rnn_states, prev_actions, action_masks)
+        fused_head = self._fused_head_eligible(observations, None)
+        # (order: when the persistent depth encoder is the neighbour, the bi-LSTM - 340 registers per SIMD lane - cannot
+        #  be scheduled before that launch ends; last in this graph it delays nothing else - graphed.py sets txt_last)
+        last = step.txt_last and not step.txt_with_dep
+        if not last and not step.txt_with_dep:
+            txt3 = self._txt_branch(observations, fused_head, None)
+        map2 = self._map_branch(observations, step.state_in, None)
+        if last:
+            txt3 = self._txt_branch(observations, fused_head, None)
+        self._prev_embed(prev_actions, masks_u8, step.state_in, step.x2)
+        return txt3, map2
+
+    def stage_post(self, observations, rnn_states, prev_actions, action_masks, step, dep2, pre, rnn_out=None):
+        """The head, behind both other graphs: `dep2` from stage_depth, `pre` = (txt3, map2) from stage_pre."""
+        rnn_states, masks_u8, _ = self._step_inputs(rnn_states, prev_actions, action_masks)
+        return self._head(rnn_states, masks_u8, step.state_in, step.x2, pre[0], dep2, pre[1],
+                          self._fused_head_eligible(observations, None), rnn_out)
 
     def forward(self, observations, rnn_states, prev_actions, action_masks, episode_masks=None, tour_masks=None):
         """Same signature/return as the reference forward (map_cma_policy.py:276-368); the MapCMA net
@@ -496,7 +534,6 @@ class MapCMANet(Net):
 
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in all_params(self))
         if needs_grad:
-
             feats, rnn_out = MapCMAForwardFn.run(self, observations, rnn_states, prev_actions, action_masks)
         else:
             feats, rnn_out = self.forward_hip(observations, rnn_states, prev_actions, action_masks)
@@ -525,10 +562,10 @@ class ILPolicy(Policy):
     U_SAMPLE, U_BETA = "_u_sample", "_u_beta"
     collect_mix = None  # {"beta": float, "expert_uuid": str} while a DAgger collection mixes in-kernel
 
-    def _act(self, features, deterministic, observations=None):
+    def _act(self, features, deterministic, observations=None, out=None):
+        """Action head.  `out`: the buffer a captured step (graphed.py) wants the action kernel to write into."""
         lin = self.action_distribution.linear
         small = features.is_cuda and lin.out_features <= 8 and features.stride(-1) == 1
-        out = getattr(self, "_action_out_buffer", None)
         if deterministic:  # distribution.mode() == argmax of probs == argmax of logits: head + argmax, one launch
             if small:
                 return ops.linear_argmax(features, lin.weight, lin.bias, out=out)

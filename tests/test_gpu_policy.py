@@ -165,6 +165,59 @@ def test_graphed_multistream_rollout_is_bit_identical_to_eager(streams, depth_mo
     tr_g.mapping_module.check_status()
 
 
+@pytest.mark.parametrize("streams", [True, False, "split"])
+def test_graphed_rollout_hangs_nothing_on_the_policy(streams, same_depth_path):
+    """A runner's capture and replays add no attribute to the policy or its net (streams, buffers and what joins the split
+    stages are the runner's), and an eager `act` on the same inputs returns the same bits before the runner exists,
+    while it lives and after it is gone."""
+    same_depth_path(0)
+    import gc
+
+    from ivln_ce_amd.config import get_config
+    from ivln_ce_amd.graphed import GraphedRollout
+    from ivln_ce_amd.obs_transforms import GTSemanticsIterativeMapper
+    from ivln_ce_amd.synthetic import SyntheticRollout
+
+    dev = torch.device("cuda:0")
+    pol = make_policy()
+    cfg = get_config()
+    B, steps = 4, 3
+    roll = SyntheticRollout(B=B, seed=31)
+    obs = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in roll.step().items()} for _ in range(steps)]
+    b0 = GTSemanticsIterativeMapper.from_config(cfg)(dict(obs[0]))
+    g = torch.Generator().manual_seed(5)
+    rnn0 = (0.1 * torch.randn(B, 2, 512, generator=g)).to(dev)
+    prev0 = torch.randint(0, 4, (B, 1), generator=g).to(dev)
+    masks0 = torch.tensor([[0], [1], [1], [0]], dtype=b0["not_done_masks"].dtype, device=dev)
+
+    def eager():
+        with torch.no_grad():
+            a, r = pol.act(b0, rnn0, prev0, masks0, deterministic=True)
+        torch.cuda.synchronize()
+        return a.clone(), r.clone()
+
+    before = eager()  # (also creates what the net caches lazily: the folded instruction-side weights)
+    net_vars, pol_vars = set(vars(pol.net)), set(vars(pol))
+    tr_g = GTSemanticsIterativeMapper.from_config(cfg)
+    runner = GraphedRollout(pol, [tr_g], obs[0], deterministic=True, streams=streams)
+    tr_g.mapping_module.reset()
+    runner.reset_state()
+    for o in obs:
+        runner.step(o)
+    torch.cuda.synchronize()
+    assert set(vars(pol.net)) == net_vars, sorted(set(vars(pol.net)) ^ net_vars)
+    assert set(vars(pol)) == pol_vars, sorted(set(vars(pol)) ^ pol_vars)
+    during = eager()
+    del runner
+    gc.collect()
+    after = eager()
+    assert set(vars(pol.net)) == net_vars and set(vars(pol)) == pol_vars
+    for name, (a, r) in (("beside the runner", during), ("after the runner", after)):
+        assert torch.equal(a, before[0]), f"actions {name}"
+        assert torch.equal(r, before[1]), f"states {name}"
+    tr_g.mapping_module.check_status()
+
+
 @pytest.mark.parametrize("lens", [[1, 200, 37, 200], [200], [1, 1]])
 def test_act_instruction_length_extremes_match_oracle(lens):
     """Instruction of one token and of the maximum 200 tokens (no padding at all) in the same batch: packed
