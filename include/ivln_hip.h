@@ -501,7 +501,9 @@ int ivln_embed_lengths(const int64_t* tokens, const float* table, int B, int L, 
 /* Inference fold of the same front end with the bi-LSTM's input projections (instruction_encoder.py:70-94):
  * table (V, 2G) = embedding . [W_ih ; W_ih_reverse]^T + [b_ih ; b_ih_reverse] (built by the caller with
  * ivln_gemm_f32 whenever the weights change), row_nonzero u8 (V) = the embedding row has a non-zero element.
- * tokens i64 (B,L) -> gx_f, gx_r (B*L, G) = the two halves of the token's table row, lengths i32 (B). */
+ * tokens i64 (B,L) -> gx_f, gx_r (B*L, G) = the two halves of the token's table row, lengths i32 (B).
+ * G is the cell's gate width, 4H (nn.LSTM) or 3H (nn.GRU, instruction_encoder.py:27-32).  Two directions: a NULL gx_r is
+ * IVLN_E_INVALID (one direction: ivln_embed_gates_dirs_f32). */
 int ivln_embed_gates_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
                          float* gx_f, float* gx_r, int* lengths, void* stream);
 /* The same with a per-row cache: the reference re-encodes an episode's instruction at every step (map_cma_policy.py:293,
@@ -512,6 +514,11 @@ int ivln_embed_gates_f32(const int64_t* tokens, const float* table, const uint8_
  * persistent buffers too).  Both NULL = ivln_embed_gates_f32. */
 int ivln_embed_gates_cached_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
                                 float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream);
+/* The same front end with the encoder's direction count stated (instruction_encoder.py:27-32 `bidirectional`, :70-94):
+ * ndir == 2 is ivln_embed_gates_cached_f32; ndir == 1: table (V, G) = embedding . W_ih^T + b_ih, only gx_f is written and
+ * gx_r must be NULL.  ndir and gx_r that disagree are IVLN_E_INVALID.  cache_tokens / dirty both NULL = no cache. */
+int ivln_embed_gates_dirs_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
+                              int ndir, float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream);
 /* nn.LSTM(bidirectional) over packed sequences (instruction_encoder.py:84-94): gx_* = W_ih x + b_ih
  * for all (b,t) as (B*L, 4H); out (B, 2H, L), zero for t >= lengths[b].  H must be 128. */
 int ivln_lstm_bidir_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
@@ -531,6 +538,37 @@ int ivln_lstm_bidir_fwd_cached_f32(const float* gx_f, const float* gx_r, const f
                                    const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
                                    float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty,
                                    void* stream);
+/* The same recurrence for `bidirectional` True or False (instruction_encoder.py:27-32, 49: the output width is
+ * hidden_size * (1 + bidirectional)): ndir in {1, 2} sets the grid (ndir * B items), out (B, ndir*H, L) and the saves
+ * save_gates (B, ndir, L, 4H) / save_c (B, ndir, L, H).  With ndir == 1 the *_r pointers are ignored (may be NULL).
+ * ticket / spare / dirty as above (NULL, 1, NULL = the plain launch).  ivln_lstm_bidir_fwd_* are this with ndir = 2. */
+int ivln_lstm_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
+                           const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out,
+                           float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty, void* stream);
+/* nn.GRU(E, H, bidirectional = ndir == 2) over pack_padded_sequence, then pad_packed_sequence(...).permute(0, 2, 1)
+ * (instruction_encoder.py:27-32 with rnn_type GRU, :84-94).  gx_* (B*L, 3H) = W_ih x + b_ih of all positions, whh_* (3H, H),
+ * bhh_* (3H), lengths i32 (B); torch's gate order r, z, n and n = tanh(gi_n + r * (W_hn h + b_hn)),
+ * h' = (1 - z) * n + z * h.  out (B, ndir*H, L), exactly zero for t >= min(lengths[b], L); the reverse direction runs
+ * t = len-1 .. 0; a length of 0 leaves zeros.  save (optional, BPTT) (B, ndir, L, 4, H): r, z, n, W_hn h + b_hn.  dirty i32 (B)
+ * or NULL as in ivln_lstm_bidir_fwd_cached_f32: rows with dirty == 0 are not run and `out` keeps their values.  With
+ * ndir == 1 the *_r pointers are ignored.  H must be 128 (else IVLN_E_UNSUPPORTED).  A plain launch: no ticket / spare form. */
+int ivln_gru_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
+                          const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out, float* save,
+                          const int* dirty, void* stream);
+/* (The BPTT of the two entry points above is declared beside them: the instruction encoder's options as one group; their
+ * per-kernel tests are tests/test_gpu_instruction_options.py.)
+ * BPTT of ivln_lstm_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd): dout / out (B, ndir*H, L), saves as
+ * the forward wrote them; with ndir == 1 the *_r pointers are ignored.  ivln_lstm_bidir_bwd_f32 is this with ndir = 2. */
+int ivln_lstm_dirs_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs, const float* whh_f,
+                           const float* whh_r, const int* lengths, int B, int L, int H, int ndir, float* dgx_f, float* dgx_r,
+                           float* hprev_f, float* hprev_r, void* stream);
+/* BPTT of ivln_gru_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd): dout (B, ndir*H, L), `save` and `out`
+ * of the forward -> per direction dgi (B*L, 3H), the gradient of W_ih x + b_ih (feeds W_ih, b_ih, the embedding), dgh
+ * (B*L, 3H), the gradient of W_hh h + b_hh (its n rows carry the factor r; feeds W_hh, b_hh), hprev (B*L, H) = h_{t-1} in
+ * processing order.  All three exactly zero for t >= min(lengths[b], L); dout there is not read.  H must be 128. */
+int ivln_gru_dirs_bwd_f32(const float* dout, const float* out, const float* save, const float* whh_f, const float* whh_r,
+                          const int* lengths, int B, int L, int H, int ndir, float* dgi_f, float* dgi_r, float* dgh_f,
+                          float* dgh_r, float* hprev_f, float* hprev_r, void* stream);
 /* The two consumers of an encoder's feature map in the MapCMA head in ONE launch (models/map_cma_policy.py:156-171,
  * 180-185, 276-296): feat (rows, C, P) contiguous ->  kv (rows, Ckv, P) = nn.Conv1d(C, Ckv, 1)  and
  * lin[r*ld_lin + o] = act(nn.Linear(C*P, O) of the flattened row).  rows <= 8 and rows*C*P*4 B <= 150 KB of LDS,

@@ -24,6 +24,8 @@ SOURCES = {
     "cma_step.hip": [],
     "gru_seq.hip": [],
     "lstm_state.hip": [],
+    # (GRU instruction encoder: its register arrays are indexed by fully unrolled loops only - 0 scratch bytes)
+    "instr_rnn.hip": [],
     "nn_ops.hip": [],
     "train_ops.hip": [],
     "dtw.cpp": [],

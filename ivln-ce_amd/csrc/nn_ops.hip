@@ -622,6 +622,9 @@ __global__ __launch_bounds__(1024) void k_embed_lengths(const int64_t* __restric
 // launches that follow and read dirty[b] - the bi-LSTM's output and the folded attention operands keep last step's
 // values); different (a new episode, a changed instruction, a compacted batch row, an invalidated cache: tokens < 0) ->
 // the row is copied into the cache, dirty[b] = 1 and the row is encoded.  Decided on the device, so it replays in hipGraphs.
+// ND = direction count of the recurrence behind it: the table row holds ND * G floats, and with ND == 1 (a unidirectional
+// encoder, instruction_encoder.py:27-32) there is no gx_r.  G is the cell's gate width: 4H (LSTM) or 3H (GRU).
+template <int ND>
 __global__ __launch_bounds__(1024) void k_embed_gates(const int64_t* __restrict__ tokens, const float* __restrict__ table,
                                                       const uint8_t* __restrict__ row_nonzero, int L, int G, int V,
                                                       float* __restrict__ gx_f, float* __restrict__ gx_r,
@@ -644,13 +647,17 @@ __global__ __launch_bounds__(1024) void k_embed_gates(const int64_t* __restrict_
     for (int t = wave; t < L; t += nw) {
         int64_t tok = tokens[(int64_t)b * L + t];
         if (tok < 0 || tok >= V) tok = 0;
-        const float4* row = reinterpret_cast<const float4*>(table + tok * 2 * G);
+        const float4* row = reinterpret_cast<const float4*>(table + tok * ND * G);
         float4* of = reinterpret_cast<float4*>(gx_f + ((int64_t)b * L + t) * G);
-        float4* orv = reinterpret_cast<float4*>(gx_r + ((int64_t)b * L + t) * G);
         const int q = G >> 2;
-        for (int e = lane; e < q; e += 64) {
-            of[e] = row[e];
-            orv[e] = row[q + e];
+        if constexpr (ND == 2) {
+            float4* orv = reinterpret_cast<float4*>(gx_r + ((int64_t)b * L + t) * G);
+            for (int e = lane; e < q; e += 64) {
+                of[e] = row[e];
+                orv[e] = row[q + e];
+            }
+        } else {
+            for (int e = lane; e < q; e += 64) of[e] = row[e];
         }
         local += row_nonzero[tok] ? 1 : 0;
     }
@@ -684,7 +691,9 @@ __device__ __forceinline__ void lds_barrier() {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-template <int H>
+// ND = direction count (instruction_encoder.py:27-32, `bidirectional`): the grid is ND * B items, out is (B, ND*H, L) and
+// the saves are (B, ND, L, .); with ND == 1 every item is a forward one and the *_r pointers are never read.
+template <int H, int ND>
 __global__ __launch_bounds__(4 * H) void k_lstm_bidir(const float* __restrict__ gx_f,
                                                       const float* __restrict__ gx_r,
                                                       const float* __restrict__ whh_f,
@@ -711,7 +720,7 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bidir(const float* __restrict__ 
         }
         __syncthreads();
         item = s_item;
-        if (item >= 2 * B) return;
+        if (item >= ND * B) return;
     }
     if (dirty && !dirty[item % B]) return;  // (per-episode cache, k_embed_gates: this row's output of last step stands)
     // Quad j (threads 4j..4j+3) owns hidden unit j: lane q multiplies the 4 gate rows {i,f,g,o} of unit j
@@ -775,14 +784,14 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bidir(const float* __restrict__ 
         const float e = __expf(q == 2 ? -2.f * acc : -acc);
         const float rc = __builtin_amdgcn_rcpf(1.f + e);
         const float a = q == 2 ? 2.f * rc - 1.f : rc;
-        if (save_gates) save_gates[(((int64_t)b * 2 + dir) * L + t) * G + g] = a;
+        if (save_gates) save_gates[(((int64_t)b * ND + dir) * L + t) * G + g] = a;
         const float ai = quad_perm<0x00>(a), af = quad_perm<0x55>(a), ag = quad_perm<0xAA>(a), ao = quad_perm<0xFF>(a);
         c = af * c + ai * ag;
         const float h = ao * (2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * c)) - 1.f);
         if (q == 0) {
             hs[(s + 1) & 1][hslot] = h;
-            out[((int64_t)b * 2 * H + dir * H + j) * L + t] = h;
-            if (save_c) save_c[(((int64_t)b * 2 + dir) * L + t) * H + j] = c;
+            out[((int64_t)b * ND * H + dir * H + j) * L + t] = h;
+            if (save_c) save_c[(((int64_t)b * ND + dir) * L + t) * H + j] = c;
         }
         lds_barrier();
     };
@@ -801,7 +810,7 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bidir(const float* __restrict__ 
         g3 = gx_at(s + 7);
     }
     if (q == 0)
-        for (int t = len; t < L; ++t) out[((int64_t)b * 2 * H + dir * H + j) * L + t] = 0.f;
+        for (int t = len; t < L; ++t) out[((int64_t)b * ND * H + dir * H + j) * L + t] = 0.f;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1634,11 +1643,21 @@ int ivln_embed_gates_f32(const int64_t* tokens, const float* table, const uint8_
 
 int ivln_embed_gates_cached_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
                                 float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream) {
-    if (!tokens || !table || !row_nonzero || !gx_f || !gx_r || !lengths || B <= 0 || L <= 0 || G <= 0 || (G & 3) || V <= 0)
+    return ivln_embed_gates_dirs_f32(tokens, table, row_nonzero, B, L, G, V, 2, gx_f, gx_r, lengths, cache_tokens, dirty, stream);
+}
+
+int ivln_embed_gates_dirs_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
+                              int ndir, float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream) {
+    if (!tokens || !table || !row_nonzero || !gx_f || !lengths || B <= 0 || L <= 0 || G <= 0 || (G & 3) || V <= 0)
         return IVLN_E_INVALID;
+    if ((ndir != 1 && ndir != 2) || (ndir == 2) != (gx_r != nullptr)) return IVLN_E_INVALID;
     if ((cache_tokens == nullptr) != (dirty == nullptr)) return IVLN_E_INVALID;
-    hipLaunchKernelGGL(k_embed_gates, dim3(B), dim3(1024), 0, (hipStream_t)stream, tokens, table, row_nonzero, L, G, V, gx_f,
-                       gx_r, lengths, cache_tokens, dirty);
+    if (ndir == 2)
+        hipLaunchKernelGGL(k_embed_gates<2>, dim3(B), dim3(1024), 0, (hipStream_t)stream, tokens, table, row_nonzero, L, G, V,
+                           gx_f, gx_r, lengths, cache_tokens, dirty);
+    else  // one direction: table (V, G)
+        hipLaunchKernelGGL(k_embed_gates<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, tokens, table, row_nonzero, L, G, V,
+                           gx_f, gx_r, lengths, cache_tokens, dirty);
     return LAUNCH_OK();
 }
 
@@ -1660,10 +1679,22 @@ int ivln_lstm_bidir_fwd_cached_f32(const float* gx_f, const float* gx_r, const f
                                    const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
                                    float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty,
                                    void* stream) {
+    return ivln_lstm_dirs_fwd_f32(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, 2, out, save_gates, save_c, ticket,
+                                  spare, dirty, stream);
+}
+
+int ivln_lstm_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
+                           const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out,
+                           float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty, void* stream) {
     if (H != 128) return IVLN_E_UNSUPPORTED;
-    if (B <= 0 || spare < 1 || spare > 8 || (spare > 1 && !ticket)) return IVLN_E_INVALID;
-    hipLaunchKernelGGL((k_lstm_bidir<128>), dim3(2 * B * (ticket ? spare : 1)), dim3(512), 0, (hipStream_t)stream, gx_f, gx_r,
-                       whh_f, whh_r, bhh_f, bhh_r, lengths, L, out, save_gates, save_c, B, ticket, dirty);
+    if (B <= 0 || L <= 0 || spare < 1 || spare > 8 || (spare > 1 && !ticket) || (ndir != 1 && ndir != 2)) return IVLN_E_INVALID;
+    if (!gx_f || !whh_f || !bhh_f || !lengths || !out || (ndir == 2 && (!gx_r || !whh_r || !bhh_r))) return IVLN_E_INVALID;
+    if (ndir == 2)
+        hipLaunchKernelGGL((k_lstm_bidir<128, 2>), dim3(2 * B * (ticket ? spare : 1)), dim3(512), 0, (hipStream_t)stream, gx_f,
+                           gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, L, out, save_gates, save_c, B, ticket, dirty);
+    else
+        hipLaunchKernelGGL((k_lstm_bidir<128, 1>), dim3(B * (ticket ? spare : 1)), dim3(512), 0, (hipStream_t)stream, gx_f,
+                           gx_f, whh_f, whh_f, bhh_f, bhh_f, lengths, L, out, save_gates, save_c, B, ticket, dirty);
     return LAUNCH_OK();
 }
 

@@ -427,7 +427,8 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-template <int H>
+// ND = direction count of the forward (k_lstm_bidir<H, ND>): grid (B, ND), dout / out are (B, ND*H, L), saves (B, ND, L, .).
+template <int H, int ND>
 __global__ __launch_bounds__(4 * H) void k_lstm_bidir_bwd(const float* __restrict__ dout,
                                                           const float* __restrict__ out,
                                                           const float* __restrict__ gates,
@@ -471,10 +472,10 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bidir_bwd(const float* __restric
         }
     }
     lds_barrier();
-    const float* gt = gates + ((int64_t)b * 2 + dir) * L * G;
-    const float* ct = cs + ((int64_t)b * 2 + dir) * L * H;
+    const float* gt = gates + ((int64_t)b * ND + dir) * L * G;
+    const float* ct = cs + ((int64_t)b * ND + dir) * L * H;
     const int j = tid;  // element part: threads 0..H-1 own hidden unit j
-    const int64_t orow = ((int64_t)b * 2 * H + dir * H + (j < H ? j : 0)) * L;
+    const int64_t orow = ((int64_t)b * ND * H + dir * H + (j < H ? j : 0)) * L;
     float dcc = 0.f;    // dc carried to the previous timestep (register: only thread j touches it)
     // inputs of a timestep: gates i,f,g,o, c, c_prev, h_prev, dout
     float n_i = 0.f, n_f = 0.f, n_g = 0.f, n_o = 0.f, n_c = 0.f, n_cp = 0.f, n_hp = 0.f, n_do = 0.f;
@@ -1165,9 +1166,22 @@ int ivln_linear_skinny_ex_f32(const float* x, int64_t ldx, const float* W, const
 int ivln_lstm_bidir_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs,
                             const float* whh_f, const float* whh_r, const int* lengths, int B, int L, int H,
                             float* dgx_f, float* dgx_r, float* hprev_f, float* hprev_r, void* stream) {
+    return ivln_lstm_dirs_bwd_f32(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, 2, dgx_f, dgx_r, hprev_f, hprev_r, stream);
+}
+
+int ivln_lstm_dirs_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs, const float* whh_f,
+                           const float* whh_r, const int* lengths, int B, int L, int H, int ndir, float* dgx_f, float* dgx_r,
+                           float* hprev_f, float* hprev_r, void* stream) {
     if (H != 128) return IVLN_E_UNSUPPORTED;
-    hipLaunchKernelGGL((k_lstm_bidir_bwd<128>), dim3(B, 2), dim3(512), 0, (hipStream_t)stream, dout, out, gates, cs,
-                       whh_f, whh_r, lengths, L, dgx_f, dgx_r, hprev_f, hprev_r);
+    if (B <= 0 || L <= 0 || (ndir != 1 && ndir != 2)) return IVLN_E_INVALID;
+    if (!dout || !out || !gates || !cs || !whh_f || !lengths || !dgx_f || !hprev_f) return IVLN_E_INVALID;
+    if (ndir == 2 && (!whh_r || !dgx_r || !hprev_r)) return IVLN_E_INVALID;
+    if (ndir == 2)
+        hipLaunchKernelGGL((k_lstm_bidir_bwd<128, 2>), dim3(B, 2), dim3(512), 0, (hipStream_t)stream, dout, out, gates, cs,
+                           whh_f, whh_r, lengths, L, dgx_f, dgx_r, hprev_f, hprev_r);
+    else
+        hipLaunchKernelGGL((k_lstm_bidir_bwd<128, 1>), dim3(B, 1), dim3(512), 0, (hipStream_t)stream, dout, out, gates, cs,
+                           whh_f, whh_f, lengths, L, dgx_f, dgx_f, hprev_f, hprev_f);
     return LAUNCH_OK();
 }
 

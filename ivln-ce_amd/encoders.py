@@ -156,11 +156,19 @@ class SemanticMapEncoder(nn.Module):
 # Instruction encoder
 # ------------------------------------------------------------------------------------------------
 class InstructionEncoder(nn.Module):
+    """instruction_encoder.py:11-94.  `rnn_type` selects nn.GRU or nn.LSTM and `bidirectional` the direction count (:27-32);
+    the output width is hidden_size * (1 + bidirectional) (:49).  The torch module only holds the parameters, so the
+    state-dict keys are the reference's: no `*_reverse` entries when unidirectional."""
+
     def __init__(self, config) -> None:
         super().__init__()
         self.config = config
-        assert config.rnn_type == "LSTM" and config.bidirectional, "MapCMA uses a bidirectional LSTM"
-        self.encoder_rnn = nn.LSTM(input_size=config.embedding_size, hidden_size=config.hidden_size, bidirectional=True)
+        kind = str(config.rnn_type).upper()
+        if kind not in ("GRU", "LSTM"):
+            raise ValueError(f"MODEL.INSTRUCTION_ENCODER.rnn_type must be GRU or LSTM, got {config.rnn_type!r}")
+        rnn = nn.GRU if kind == "GRU" else nn.LSTM
+        self.encoder_rnn = rnn(input_size=config.embedding_size, hidden_size=config.hidden_size,
+                               bidirectional=bool(config.bidirectional))
         if config.sensor_uuid == "instruction":
             if config.use_pretrained_embeddings:
                 self.embedding_layer = nn.Embedding.from_pretrained(
@@ -173,25 +181,46 @@ class InstructionEncoder(nn.Module):
 
     @property
     def output_size(self):
-        return self.config.hidden_size * 2
+        return self.config.hidden_size * (1 + int(bool(self.config.bidirectional)))
+
+    @property
+    def is_gru(self):
+        return isinstance(self.encoder_rnn, nn.GRU)
+
+    @property
+    def ndir(self):
+        return 2 if self.encoder_rnn.bidirectional else 1
+
+    @property
+    def gates(self):
+        """Gate rows per hidden unit: 3 (GRU: r, z, n) or 4 (LSTM: i, f, g, o)."""
+        return 3 if self.is_gru else 4
+
+    def dir_params(self, stem):
+        """The `stem` parameter ("weight_ih", "weight_hh", "bias_ih", "bias_hh") of every direction that exists:
+        (forward,) or (forward, reverse)."""
+        rnn = self.encoder_rnn
+        names = (stem + "_l0",) if self.ndir == 1 else (stem + "_l0", stem + "_l0_reverse")
+        return tuple(getattr(rnn, n) for n in names)
 
     def _load_embeddings(self):
         with gzip.open(self.config.embedding_file, "rt") as f:
             return torch.tensor(json.load(f))
 
     def _gate_table(self):
-        """(table (V, 8H), row_nonzero u8 (V)) of ivln_embed_gates_f32, cached until a weight changes; None while a
-        stream capture is running and no valid table exists (the caller then runs the unfolded launches)."""
-        rnn, E = self.encoder_rnn, self.embedding_layer.weight
-        ps = (E, rnn.weight_ih_l0, rnn.weight_ih_l0_reverse, rnn.bias_ih_l0, rnn.bias_ih_l0_reverse)
+        """(table (V, ndir * gates * H), row_nonzero u8 (V)) of ivln_embed_gates_f32, cached until a weight changes; None
+        while a stream capture is running and no valid table exists (the caller then runs the unfolded launches)."""
+        E = self.embedding_layer.weight
+        ws, bs = self.dir_params("weight_ih"), self.dir_params("bias_ih")
+        ps = (E,) + ws + bs
         key = (ops.WEIGHT_EPOCH,) + tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps)
         c = self.__dict__.get("_gate_cache")
         if c is None or c[0] != key:
             if torch.cuda.is_current_stream_capturing():
                 return None
             with torch.no_grad():
-                W = torch.cat([rnn.weight_ih_l0, rnn.weight_ih_l0_reverse]).contiguous()
-                b = torch.cat([rnn.bias_ih_l0, rnn.bias_ih_l0_reverse]).contiguous()
+                W = torch.cat(list(ws)).contiguous()
+                b = torch.cat(list(bs)).contiguous()
                 table = ops.linear_gemm(E.detach().contiguous(), W, b)
                 nz = (E.detach() != 0).any(dim=1).to(torch.uint8).contiguous()
             c = self.__dict__["_gate_cache"] = (key, (table, nz))
@@ -200,13 +229,14 @@ class InstructionEncoder(nn.Module):
     def step_cache(self, rows, L, device):
         """The per-episode cache of a rollout batch shape (ops.InstructionStepCache), or None: switched off, a capture in
         progress that would have to create or invalidate it (the warm-up steps before a capture do that), no folded table.
-        A cache made for other weights (LSTM / embedding versions, ops.WEIGHT_EPOCH) is invalidated, not rebuilt: captured
-        graphs hold its buffers."""
+        A cache made for other weights (recurrent / embedding versions, ops.WEIGHT_EPOCH) is invalidated, not rebuilt:
+        captured graphs hold its buffers.  The key names the recurrent parameters that exist for the combination."""
         if not ops.CACHE_INSTRUCTION:
             return None
         gate_key = (self.__dict__.get("_gate_cache") or (None,))[0]
         rnn = self.encoder_rnn
-        ps = (rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, rnn.bias_hh_l0, rnn.bias_hh_l0_reverse)
+        ws, bs = self.dir_params("weight_hh"), self.dir_params("bias_hh")
+        ps = ws + bs
         key = (gate_key,) + tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps)
         caches = self.__dict__.setdefault("_step_caches", {})
         c = caches.get((rows, L, str(device)))
@@ -216,7 +246,8 @@ class InstructionEncoder(nn.Module):
                 return None
             if len(caches) >= 4:  # (batch shapes come and go as envs pause: keep the table small)
                 caches.pop(next(iter(caches)))
-            c = caches[(rows, L, str(device))] = ops.InstructionStepCache(rows, L, 4 * rnn.hidden_size, rnn.hidden_size, device, key)
+            c = caches[(rows, L, str(device))] = ops.InstructionStepCache(rows, L, self.gates * rnn.hidden_size, rnn.hidden_size,
+                                                                          device, key, ndir=self.ndir)
         elif c.key != key:
             if capturing:
                 return None
@@ -224,41 +255,50 @@ class InstructionEncoder(nn.Module):
             c.key = key
         return c
 
+    def _recurrence(self, gx_f, gx_r, lengths, B, L, save=False, cache=None):
+        """The packed-sequence recurrence of the configured cell and direction count -> (out (B, ndir*H, L), saves dict)."""
+        H, nd = self.encoder_rnn.hidden_size, self.ndir
+        whh, bhh = self.dir_params("weight_hh"), self.dir_params("bias_hh")
+        whh_r, bhh_r = (whh[1], bhh[1]) if nd == 2 else (None, None)
+        if self.is_gru:
+            # (no ticket / spare form of the GRU kernel: graphed.py leaves lstm_spare at 1 for a GRU encoder)
+            out, sv = ops.gru_dirs(gx_f, gx_r, whh[0], whh_r, bhh[0], bhh_r, lengths, B, L, H, ndir=nd, save=save, cache=cache)
+            return out, dict(gru=sv)
+        out, gates, cs = ops.lstm_bidir(gx_f, gx_r, whh[0], whh_r, bhh[0], bhh_r, lengths, B, L, H, save=save,
+                                        spare=getattr(self, "lstm_spare", 1), ticket=getattr(self, "lstm_ticket", None),
+                                        cache=cache, ndir=nd)
+        return out, dict(gates=gates, cs=cs)
+
     def forward(self, observations, save=None):
-        """(B, L) tokens -> (B, 2H, L) channel-major outputs, zero for t >= length; also returns
-        lengths (device int32).  The reference returns (B, 2H, Lmax); the extra columns here are
+        """(B, L) tokens -> (B, ndir*H, L) channel-major outputs, zero for t >= length; also returns
+        lengths (device int32).  The reference returns (B, ndir*H, Lmax); the extra columns here are
         exactly the masked (zero-weight) attention positions.
         Rollout steps (no `save`, no autograd): the encoding is cached per row and recomputed only where the tokens
         changed (`step_cache`; the decision is taken on the device, ops.embed_gates) - `self.last_cache` then names the
         cache whose `dirty` flags belong to this call, else it is None."""
         tokens = observations["instruction"].long().contiguous()
         B, L = tokens.shape
-        rnn = self.encoder_rnn
-        H = rnn.hidden_size
+        nd = self.ndir
         fold = self._gate_table() if (save is None and ops.FOLD_INSTRUCTION_GATES) else None
         self.last_cache = None
         if fold is not None and tokens.is_cuda and not torch.is_grad_enabled():
             cache = self.step_cache(B, L, tokens.device)
             if cache is not None:
-                gx_f, gx_r, lengths = ops.embed_gates(tokens, *fold, cache=cache)
-                out, _, _ = ops.lstm_bidir(gx_f, gx_r, rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, rnn.bias_hh_l0,
-                                           rnn.bias_hh_l0_reverse, lengths, B, L, H, spare=getattr(self, "lstm_spare", 1),
-                                           ticket=getattr(self, "lstm_ticket", None), cache=cache)
+                gx_f, gx_r, lengths = ops.embed_gates(tokens, *fold, cache=cache, ndir=nd)
+                out, _ = self._recurrence(gx_f, gx_r, lengths, B, L, cache=cache)
                 self.last_cache = cache
                 return out, lengths
-        if fold is not None:  # inference: embedding lookup + both W_ih projections = one lookup in a folded table
+        if fold is not None:  # inference: embedding lookup + the W_ih projections = one lookup in a folded table
             emb = None
-            gx_f, gx_r, lengths = ops.embed_gates(tokens, *fold)
+            gx_f, gx_r, lengths = ops.embed_gates(tokens, *fold, ndir=nd)
         else:
             emb, lengths = ops.embed_lengths(tokens, self.embedding_layer.weight)
-            gx_f = ops.linear_gemm(emb, rnn.weight_ih_l0, rnn.bias_ih_l0)
-            gx_r = ops.linear_gemm(emb, rnn.weight_ih_l0_reverse, rnn.bias_ih_l0_reverse)
-        out, gates, cs = ops.lstm_bidir(
-            gx_f, gx_r, rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, rnn.bias_hh_l0, rnn.bias_hh_l0_reverse, lengths,
-            B, L, H, save=save is not None, spare=getattr(self, "lstm_spare", 1), ticket=getattr(self, "lstm_ticket", None),
-        )
+            wih, bih = self.dir_params("weight_ih"), self.dir_params("bias_ih")
+            gx_f = ops.linear_gemm(emb, wih[0], bih[0])
+            gx_r = ops.linear_gemm(emb, wih[1], bih[1]) if nd == 2 else None
+        out, sv = self._recurrence(gx_f, gx_r, lengths, B, L, save=save is not None)
         if save is not None:
-            save.update(emb=emb, lengths=lengths, gates=gates, cs=cs, out=out, tokens=tokens)
+            save.update(emb=emb, lengths=lengths, out=out, tokens=tokens, **sv)
         return out, lengths
 
 

@@ -296,7 +296,8 @@ class GraphedRollout:
         # (2B * spare blocks so that 2B of them land on the 8 - B free XCDs; measured at 4 and 5 images: 667 -> 620 us per
         #  step; at 6 and 7 - spare 4 and 8 - the recurrence still started only when the depth encoder ended: left alone)
         spare = int(os.environ.get("IVLN_LSTM_SPARE", str(2 if B <= 4 else 3 if B == 5 else 1)))
-        if step.txt_last and not predicted and spare > 1 and B < 8:
+        # (a GRU instruction encoder has no ticket form - csrc/instr_rnn.hip is a plain launch: spare stays 1)
+        if step.txt_last and not predicted and spare > 1 and B < 8 and not ienc.is_gru:
             # (the captured launches hold this word's ADDRESS: it lives as long as this object's graphs, whatever a later
             #  capture of the same policy hangs on the module)
             self._lstm_ticket = ienc.lstm_ticket = torch.zeros((1,), dtype=torch.int32, device=dev)

@@ -248,7 +248,7 @@ class LatentCMANet(Net):
                 tk = ops.conv2d(txt.view(txt.shape[0], -1, 1, txt.shape[2]), self.text_k.weight.view(h2, -1, 1, 1),
                                 shift=self.text_k.bias, splitk=False)
         else:
-            txt, lengths = self.instruction_encoder(observations, s_txt)  # (rows, 256, L), zero beyond each length
+            txt, lengths = self.instruction_encoder(observations, s_txt)  # (rows, Ct, L), zero beyond each length
             tk = None
         dep = self.depth_encoder(observations)                         # (rows, 192, 4, 4)
         rgb = self.rgb_encoder(observations)                           # (rows, 2112, 4, 4)
@@ -267,8 +267,9 @@ class LatentCMANet(Net):
         # state_in = [rgb_in | depth_in | prev (| tour memory)];  x2 = [state | text | rgb' | depth' | prev]
         base = r_out + d_out + E
         state_in = torch.empty((rows, base + (H if variant else 0)), dtype=torch.float32, device=dev)
-        x2 = torch.empty((rows, H + 256 + r_out + d_out + E), dtype=torch.float32, device=dev)
-        o_txt, o_rgb, o_dep, o_prev = H, H + 256, H + 256 + r_out, H + 256 + r_out + d_out
+        Ct = self.instruction_encoder.output_size  # hidden_size * (1 + bidirectional)
+        x2 = torch.empty((rows, H + Ct + r_out + d_out + E), dtype=torch.float32, device=dev)
+        o_txt, o_rgb, o_dep, o_prev = H, H + Ct, H + Ct + r_out, H + Ct + r_out + d_out
         ops.prev_action_embed(prev_actions, act_u8, self.prev_action_embedding.weight, state_in[:, r_out + d_out:base],
                               x2[:, o_prev:])
         rgb_mean = ops.pool2d(rgb, 4, 4, 0, "avg").view(rows, Cr)  # AdaptiveAvgPool1d(1) over the 16 positions
@@ -317,7 +318,7 @@ class LatentCMANet(Net):
         q1 = ops.linear(state, self.state_q.weight, self.state_q.bias)
         if tk is None:
             tk = ops.conv2d(txt.view(rows, -1, 1, L), self.text_k.weight.view(h2, -1, 1, 1), shift=self.text_k.bias, splitk=False)
-        text = x2[:, o_txt:o_txt + 256]
+        text = x2[:, o_txt:o_rgb]
         a_txt = torch.empty((rows, L), dtype=torch.float32, device=dev) if save is not None else None
         ops.attn(q1, tk.view(rows, h2, L), txt, lengths, self._scale_f, text, a_txt)
         q2 = ops.linear(text, self.text_q.weight, self.text_q.bias)
@@ -387,10 +388,10 @@ class LatentCMANet(Net):
         ops.attn_bwd(dx2[:, o_dep:o_dep + d_out], S["a_dep"], S["q2"], dkv[:, :h2], dkv[:, h2:], scale, dq2_d,
                      d_dkv[:, :h2], d_dkv[:, h2:])
         dq2 = ops.add2d(dq2_r, dq2_d)
-        text = x2[:, o_txt:o_txt + 256]
+        text = x2[:, o_txt:o_rgb]
         G[self.text_q.weight] = ops.linear_bwd_weight(dq2, text)
         G[self.text_q.bias] = ops.colsum(dq2)
-        d_text = dx2[:, o_txt:o_txt + 256]
+        d_text = dx2[:, o_txt:o_rgb]
         ops.linear_bwd_input(dq2, self.text_q.weight, out=d_text, accumulate=True)
 
         txt, tk = S["txt_out"], S["tk"]

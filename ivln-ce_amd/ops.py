@@ -1245,44 +1245,51 @@ def embed_lengths(tokens_i64, table):
     return emb, lengths
 
 
-def embed_gates(tokens_i64, table, row_nonzero, cache=None):
-    """tokens (B, L) -> gx_f, gx_r (B*L, G) looked up in the folded (V, 2G) table, lengths i32 (B) (k_embed_gates).
+def embed_gates(tokens_i64, table, row_nonzero, cache=None, ndir=2):
+    """tokens (B, L) -> gx_f, gx_r (B*L, G) looked up in the folded (V, ndir*G) table, lengths i32 (B) (k_embed_gates).
     cache: an `InstructionStepCache` - its persistent gx / lengths buffers are the outputs and only the rows whose tokens
-    differ from the cached ones are written (ivln_embed_gates_cached_f32; cache.dirty says which)."""
+    differ from the cached ones are written (ivln_embed_gates_cached_f32; cache.dirty says which).
+    ndir=1: a unidirectional encoder (ivln_embed_gates_dirs_f32) - table (V, G), gx_r is None."""
     B, L = tokens_i64.shape
     V, G2 = table.shape
-    G = G2 // 2
+    G = G2 // ndir
     Lb = _L()
-    Lb.ivln_embed_gates_cached_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     if cache is not None:
         gx_f, gx_r, lengths = cache.gx_f, cache.gx_r, cache.lengths
+        ct, dirty = dptr(cache.tokens), dptr(cache.dirty)
+    else:
+        gx_f = torch.empty((B * L, G), dtype=torch.float32, device=table.device)
+        gx_r = torch.empty((B * L, G), dtype=torch.float32, device=table.device) if ndir == 2 else None
+        lengths = torch.empty((B,), dtype=torch.int32, device=table.device)
+        ct = dirty = None
+    if ndir == 2:
+        Lb.ivln_embed_gates_cached_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         check(Lb.ivln_embed_gates_cached_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, dptr(gx_f), dptr(gx_r),
-                                             dptr(lengths), dptr(cache.tokens), dptr(cache.dirty), stream_ptr()),
-              "ivln_embed_gates_cached_f32")
-        return gx_f, gx_r, lengths
-    gx_f = torch.empty((B * L, G), dtype=torch.float32, device=table.device)
-    gx_r = torch.empty((B * L, G), dtype=torch.float32, device=table.device)
-    lengths = torch.empty((B,), dtype=torch.int32, device=table.device)
-    check(Lb.ivln_embed_gates_cached_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, dptr(gx_f), dptr(gx_r),
-                                         dptr(lengths), None, None, stream_ptr()), "ivln_embed_gates_f32")
+                                             dptr(lengths), ct, dirty, stream_ptr()),
+              "ivln_embed_gates_cached_f32" if cache is not None else "ivln_embed_gates_f32")
+    else:
+        Lb.ivln_embed_gates_dirs_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        check(Lb.ivln_embed_gates_dirs_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, ndir, dptr(gx_f),
+                                           _p(gx_r), dptr(lengths), ct, dirty, stream_ptr()), "ivln_embed_gates_dirs_f32")
     return gx_f, gx_r, lengths
 
 
 class InstructionStepCache:
     """Persistent device buffers of the per-episode instruction cache for one (rows, L) batch shape (rollout steps only:
     map_cma_policy.py:293 re-encodes an episode's instruction at every step): the tokens every row encoded last, the per-row
-    dirty flags of the current step, and everything the instruction branch produces - gate inputs, lengths, the bi-LSTM's
-    output, the folded attention operands (`fold`, allocated by the policy on first use).  Allocated OUTSIDE any stream
+    dirty flags of the current step, and everything the instruction branch produces - gate inputs (G = gates * H wide: 4H
+    for an LSTM, 3H for a GRU; no reverse set when ndir == 1), lengths, the recurrence's output (ndir * H channels), the
+    folded attention operands (`fold`, allocated by the policy on first use).  Allocated OUTSIDE any stream
     capture and shared by every graph of the policy, so that what one replayed step leaves is what the next one finds."""
 
-    def __init__(self, rows, L, G, H, device, key):
-        self.rows, self.L, self.key = rows, L, key
+    def __init__(self, rows, L, G, H, device, key, ndir=2):
+        self.rows, self.L, self.key, self.ndir = rows, L, key, ndir
         self.tokens = torch.full((rows, L), -1, dtype=torch.int64, device=device)  # (-1: no row matches - everything dirty)
         self.dirty = torch.ones((rows,), dtype=torch.int32, device=device)
         self.gx_f = torch.zeros((rows * L, G), dtype=torch.float32, device=device)
-        self.gx_r = torch.zeros((rows * L, G), dtype=torch.float32, device=device)
+        self.gx_r = torch.zeros((rows * L, G), dtype=torch.float32, device=device) if ndir == 2 else None
         self.lengths = torch.zeros((rows,), dtype=torch.int32, device=device)
-        self.out = torch.zeros((rows, 2 * H, L), dtype=torch.float32, device=device)
+        self.out = torch.zeros((rows, ndir * H, L), dtype=torch.float32, device=device)
         self.fold = None
         self.fold_key = None
         _STEP_CACHES.add(self)
@@ -1305,11 +1312,35 @@ def invalidate_step_caches():
         c.invalidate()
 
 
-def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=False, spare=1, ticket=None, cache=None):
-    """spare > 1: ivln_lstm_bidir_fwd_spread_f32 - 2B * spare blocks draw the 2B items in the order they start (for a
+def _lstm_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir, save, spare, ticket, cache):
+    """ivln_lstm_dirs_fwd_f32: the recurrence with a direction count (lstm_bidir's body for ndir != 2)."""
+    dev = gx_f.device
+    tk = ticket if spare > 1 and not save else None
+    if spare > 1 and not save and (tk is None or tk.dtype != torch.int32 or tk.device != dev):
+        raise ValueError("lstm_bidir(spare>1) needs the caller's int32 ticket word on the same device")
+    cached = cache is not None and not save
+    out = cache.out if cached else torch.empty((B, ndir * H, L), dtype=torch.float32, device=dev)
+    gates = cs = None
+    if save:
+        gates = torch.zeros((B, ndir, L, 4 * H), dtype=torch.float32, device=dev)
+        cs = torch.zeros((B, ndir, L, H), dtype=torch.float32, device=dev)
+    Lb = _L()
+    Lb.ivln_lstm_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+    check(Lb.ivln_lstm_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L,
+                                    H, ndir, dptr(out), _p(gates), _p(cs), _p(tk), int(spare) if tk is not None else 1,
+                                    dptr(cache.dirty) if cached else None, stream_ptr()), "ivln_lstm_dirs_fwd_f32")
+    return out, gates, cs
+
+
+def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=False, spare=1, ticket=None, cache=None,
+               ndir=2):
+    """ndir=1: one direction (the *_r arguments are None), out (B, H, L), saves (B, 1, L, .).
+    spare > 1: ivln_lstm_bidir_fwd_spread_f32 - 2B * spare blocks draw the 2B items in the order they start (for a
     replay beside a launch that fills some XCDs).  ticket: the caller's zeroed int32 word (one launch in flight per word).
     cache: the step cache whose `dirty` flags `embed_gates` just wrote - rows with dirty == 0 are not run and cache.out
     (the returned tensor) keeps their values."""
+    if ndir != 2:
+        return _lstm_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir, save, spare, ticket, cache)
     if cache is not None and not save:
         tk = ticket if spare > 1 else None
         if spare > 1 and (tk is None or tk.dtype != torch.int32 or tk.device != gx_f.device):
@@ -1342,6 +1373,22 @@ def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=Fa
         "ivln_lstm_bidir_fwd_f32",
     )
     return out, gates, cs
+
+
+def gru_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir=2, save=False, cache=None):
+    """nn.GRU over packed sequences, ndir directions (ivln_gru_dirs_fwd_f32): gx_* (B*L, 3H) -> out (B, ndir*H, L), zero
+    beyond each length; `saves` (B, ndir, L, 4, H) = r, z, n, W_hn h + b_hn when `save`.  cache: as in lstm_bidir.  The *_r
+    arguments are None when ndir == 1."""
+    dev = gx_f.device
+    cached = cache is not None and not save
+    out = cache.out if cached else torch.empty((B, ndir * H, L), dtype=torch.float32, device=dev)
+    saves = torch.zeros((B, ndir, L, 4, H), dtype=torch.float32, device=dev) if save else None
+    Lb = _L()
+    Lb.ivln_gru_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp]
+    check(Lb.ivln_gru_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L, H,
+                                   ndir, dptr(out), _p(saves), dptr(cache.dirty) if cached else None, stream_ptr()),
+          "ivln_gru_dirs_fwd_f32")
+    return out, saves
 
 
 def attn_small2(q, k0, v0, out0, k1, v1, out1, scale):
@@ -1909,7 +1956,36 @@ def linear_skinny_ex(x, W, add, rowmask, out):
     return out
 
 
-def lstm_bidir_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H):
+def gru_dirs_bwd(dout, out, saves, whh_f, whh_r, lengths, B, L, H, ndir=2):
+    """BPTT of gru_dirs (ivln_gru_dirs_bwd_f32) -> (dgi, dgh, hprev) per direction: [(dgi_f, dgh_f, hp_f), (dgi_r, dgh_r,
+    hp_r)] (one entry when ndir == 1); dgi / dgh (B*L, 3H), hprev (B*L, H), zero at padded positions."""
+    dev = dout.device
+    res = [tuple(torch.empty((B * L, w), dtype=torch.float32, device=dev) for w in (3 * H, 3 * H, H)) for _ in range(ndir)]
+    f, r = res[0], (res[1] if ndir == 2 else (None, None, None))
+    Lb = _T()
+    Lb.ivln_gru_dirs_bwd_f32.argtypes = [vp] * 6 + [i32, i32, i32, i32] + [vp] * 7
+    check(Lb.ivln_gru_dirs_bwd_f32(dptr(dout), dptr(out), dptr(saves), dptr(whh_f), _p(whh_r), dptr(lengths), B, L, H, ndir,
+                                   dptr(f[0]), _p(r[0]), dptr(f[1]), _p(r[1]), dptr(f[2]), _p(r[2]), stream_ptr()),
+          "ivln_gru_dirs_bwd_f32")
+    return res
+
+
+def _lstm_dirs_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir):
+    """ivln_lstm_dirs_bwd_f32: the BPTT with a direction count (lstm_bidir_bwd's body for ndir != 2)."""
+    dev = dout.device
+    dgx = [torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev) for _ in range(ndir)] + [None]
+    hp = [torch.empty((B * L, H), dtype=torch.float32, device=dev) for _ in range(ndir)] + [None]
+    Lb = _T()
+    Lb.ivln_lstm_dirs_bwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    check(Lb.ivln_lstm_dirs_bwd_f32(dptr(dout), dptr(out), dptr(gates), dptr(cs), dptr(whh_f), _p(whh_r), dptr(lengths), B, L, H,
+                                    ndir, dptr(dgx[0]), _p(dgx[1]), dptr(hp[0]), _p(hp[1]), stream_ptr()), "ivln_lstm_dirs_bwd_f32")
+    return dgx[0], dgx[1], hp[0], hp[1]
+
+
+def lstm_bidir_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir=2):
+    """ndir=1: one direction (whh_r None) -> dgx_r / hp_r are None."""
+    if ndir != 2:
+        return _lstm_dirs_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir)
     dev = dout.device
     dgx_f = torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev)
     dgx_r = torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev)

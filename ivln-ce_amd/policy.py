@@ -438,7 +438,8 @@ class MapCMANet(Net):
         dev = rnn_states.device
         rnn_states, masks_u8, prev_actions = self._step_inputs(rnn_states, prev_actions, action_masks)
         state_in, x2 = self.step_geometry.buffers(masks_u8.shape[0], dev)
-        fused_head = self._fused_head_eligible(observations, save)
+        # (the fused head is ONE step of `rows` states: a time-major batch over fewer states takes the unfused chain)
+        fused_head = self._fused_head_eligible(observations, save) and masks_u8.shape[0] == rnn_states.shape[0]
         s_txt, s_map = ({}, []) if save is not None else (None, None)
 
         # update batches: the instruction of a trajectory is the same at every timestep, so the loader hands over the

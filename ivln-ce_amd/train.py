@@ -190,22 +190,30 @@ def _conv1d_backward(conv, d_out4, x4, d_in_residual4, G):
 
 
 def instruction_backward(ie, st, d_txt, rows, L, G):
-    """Bidirectional-LSTM BPTT of the instruction encoder (+ the embedding table when it trains)."""
-    rnn = ie.encoder_rnn
-    dgx_f, dgx_r, hp_f, hp_r = ops.lstm_bidir_bwd(d_txt.contiguous(), st["out"], st["gates"], st["cs"],
-                                                  rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, st["lengths"], rows,
-                                                  L, rnn.hidden_size)
+    """BPTT of the instruction encoder - LSTM or GRU, one or two directions (+ the embedding table when it trains)."""
+    rnn, nd, H = ie.encoder_rnn, ie.ndir, ie.encoder_rnn.hidden_size
+    wih, whh = ie.dir_params("weight_ih"), ie.dir_params("weight_hh")
+    bih, bhh = ie.dir_params("bias_ih"), ie.dir_params("bias_hh")
+    whh_r = whh[1] if nd == 2 else None
+    if ie.is_gru:
+        # the hidden-side pre-activation gradient differs from the input-side one in the n rows (the factor r)
+        per_dir = ops.gru_dirs_bwd(d_txt.contiguous(), st["out"], st["gru"], whh[0], whh_r, st["lengths"], rows, L, H, ndir=nd)
+    else:
+        dgx_f, dgx_r, hp_f, hp_r = ops.lstm_bidir_bwd(d_txt.contiguous(), st["out"], st["gates"], st["cs"], whh[0], whh_r,
+                                                      st["lengths"], rows, L, H, ndir=nd)
+        per_dir = [(dgx_f, dgx_f, hp_f), (dgx_r, dgx_r, hp_r)][:nd]
     emb_x = st["emb"]
-    G[rnn.weight_ih_l0] = ops.linear_bwd_weight(dgx_f, emb_x)
-    G[rnn.weight_ih_l0_reverse] = ops.linear_bwd_weight(dgx_r, emb_x)
-    G[rnn.weight_hh_l0] = ops.linear_bwd_weight(dgx_f, hp_f)
-    G[rnn.weight_hh_l0_reverse] = ops.linear_bwd_weight(dgx_r, hp_r)
-    bf, br = _colsum(dgx_f), _colsum(dgx_r)
-    G[rnn.bias_ih_l0], G[rnn.bias_hh_l0] = bf, bf
-    G[rnn.bias_ih_l0_reverse], G[rnn.bias_hh_l0_reverse] = br, br
+    for d, (dgi, _, _) in enumerate(per_dir):
+        G[wih[d]] = ops.linear_bwd_weight(dgi, emb_x)
+    for d, (_, dgh, hp) in enumerate(per_dir):
+        G[whh[d]] = ops.linear_bwd_weight(dgh, hp)
+    for d, (dgi, dgh, _) in enumerate(per_dir):  # (LSTM: one pre-activation sum, so one column sum serves both biases)
+        G[bih[d]] = _colsum(dgi)
+        G[bhh[d]] = G[bih[d]] if dgh is dgi else _colsum(dgh)
     if ie.embedding_layer.weight.requires_grad:
-        d_emb = ops.linear_bwd_input(dgx_f, rnn.weight_ih_l0)
-        ops.linear_bwd_input(dgx_r, rnn.weight_ih_l0_reverse, out=d_emb, accumulate=True)
+        d_emb = ops.linear_bwd_input(per_dir[0][0], wih[0])
+        if nd == 2:
+            ops.linear_bwd_input(per_dir[1][0], wih[1], out=d_emb, accumulate=True)
         g = torch.zeros_like(ie.embedding_layer.weight)
         ops.embedding_scatter_add(st["tokens"].reshape(-1), d_emb, g, ie.embedding_layer.padding_idx)
         G[ie.embedding_layer.weight] = g
@@ -273,10 +281,10 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     ops.attn_bwd(dx2[:, o_map:o_map + m_out], S["a_map"], S["q2"], mkv[:, :h2], mkv[:, h2:], scale, dq2_m,
                  d_mkv[:, :h2], d_mkv[:, h2:])
     dq2 = ops.add2d(dq2_d, dq2_m)
-    text = x2[:, o_txt:o_txt + 256]
+    text = x2[:, o_txt:o_dep]
     G[net.text_q.weight] = ops.linear_bwd_weight(dq2, text)
     G[net.text_q.bias] = _colsum(dq2)
-    d_text = dx2[:, o_txt:o_txt + 256]
+    d_text = dx2[:, o_txt:o_dep]
     ops.linear_bwd_input(dq2, net.text_q.weight, out=d_text, accumulate=True)
 
     # ---- text attention (v = the LSTM outputs themselves, k = text_k(outputs)) -------------------
