@@ -222,7 +222,7 @@ typedef struct ivln_gemm_desc {
      * output tile ALL of whose images carry 0 is skipped - neither computed nor stored, the destination keeps what it
      * held.  Device memory, read by the kernel: the decision replays in a hipGraph.  User: the folded attention operands of
      * the instruction (map_cma_policy.py:293, 320-325), recomputed only for rows whose tokens changed
-     * (ivln_embed_gates_cached_f32).  Only the float4-staged GEMM and the scalar-gather implicit GEMM honour it: the
+     * (ivln_embed_gates_dirs_f32).  Only the float4-staged GEMM and the scalar-gather implicit GEMM honour it: the
      * dispatcher sends such a call to one of them. */
     const int32_t* img_run_flags;
     /* optional: a ResNet bottleneck's TAIL as one launch (rednet.py:20-65: conv2 3x3 + bn2 + ReLU, conv3 1x1 + bn3 + residual +
@@ -498,50 +498,44 @@ int ivln_map_features_f32(const uint8_t* occ, const uint8_t* sem, float* y, int 
  * lengths i32 (B). */
 int ivln_embed_lengths(const int64_t* tokens, const float* table, int B, int L, int E, int V, float* emb,
                        int* lengths, void* stream);
-/* Inference fold of the same front end with the bi-LSTM's input projections (instruction_encoder.py:70-94):
- * table (V, 2G) = embedding . [W_ih ; W_ih_reverse]^T + [b_ih ; b_ih_reverse] (built by the caller with
- * ivln_gemm_f32 whenever the weights change), row_nonzero u8 (V) = the embedding row has a non-zero element.
- * tokens i64 (B,L) -> gx_f, gx_r (B*L, G) = the two halves of the token's table row, lengths i32 (B).
- * G is the cell's gate width, 4H (nn.LSTM) or 3H (nn.GRU, instruction_encoder.py:27-32).  Two directions: a NULL gx_r is
- * IVLN_E_INVALID (one direction: ivln_embed_gates_dirs_f32). */
-int ivln_embed_gates_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
-                         float* gx_f, float* gx_r, int* lengths, void* stream);
-/* The same with a per-row cache: the reference re-encodes an episode's instruction at every step (map_cma_policy.py:293,
- * instruction_encoder.py:72-94); the encoding is a pure function of the tokens.  cache_tokens i64 (B,L) = the tokens each
- * row encoded last (caller-owned, persistent across steps; fill with -1 to invalidate, e.g. when the weights change), dirty
- * i32 (B) = output: 1 where the row's tokens differ from the cache (the row is then encoded and the cache updated), 0 where
- * they are equal (NOTHING of the row is written: gx_f / gx_r / lengths keep their values, which therefore have to be
- * persistent buffers too).  Both NULL = ivln_embed_gates_f32. */
-int ivln_embed_gates_cached_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
-                                float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream);
-/* The same front end with the encoder's direction count stated (instruction_encoder.py:27-32 `bidirectional`, :70-94):
- * ndir == 2 is ivln_embed_gates_cached_f32; ndir == 1: table (V, G) = embedding . W_ih^T + b_ih, only gx_f is written and
- * gx_r must be NULL.  ndir and gx_r that disagree are IVLN_E_INVALID.  cache_tokens / dirty both NULL = no cache. */
+/* Inference fold of the same front end with the recurrence's input projections (instruction_encoder.py:70-94): one table
+ * lookup per token instead of the embedding lookup and the W_ih GEMMs.
+ *   table        (V, ndir * G) = embedding . [W_ih ; W_ih_reverse]^T + [b_ih ; b_ih_reverse] (ndir == 1: embedding . W_ih^T +
+ *                b_ih), built by the caller with ivln_gemm_f32 whenever the weights change
+ *   row_nonzero  u8 (V): the embedding row has a non-zero element
+ *   tokens       i64 (B, L); a token outside [0, V) reads row 0
+ *   G            the cell's gate width, 4H (nn.LSTM) or 3H (nn.GRU, instruction_encoder.py:27-32); a multiple of 4
+ *   ndir         the encoder's direction count (`bidirectional`): 2 or 1
+ *   gx_f, gx_r   outputs (B*L, G): the first / second G floats of the token's table row.  ndir == 2 needs gx_r, ndir == 1
+ *                needs gx_r == NULL; ndir and gx_r that disagree are IVLN_E_INVALID
+ *   lengths      output i32 (B): the tokens of the row whose embedding row is non-zero (the reference's
+ *                `(instruction != 0).sum(2) != 0` quirk)
+ *   cache_tokens, dirty  the per-episode cache, both or neither (one NULL alone is IVLN_E_INVALID).  The reference
+ *                re-encodes an episode's instruction at every step (map_cma_policy.py:293) and the encoding is a pure
+ *                function of the tokens.  cache_tokens i64 (B, L) = the tokens each row encoded last (caller-owned,
+ *                persistent across steps; fill with -1 to invalidate, e.g. when the weights change).  dirty i32 (B) =
+ *                output: 1 where the row's tokens differ from the cache (the row is then encoded and the cache updated), 0
+ *                where they are equal (NOTHING of the row is written: gx_f / gx_r / lengths keep their values, which
+ *                therefore have to be persistent buffers too).  Decided on the device, so it replays in hipGraphs. */
 int ivln_embed_gates_dirs_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
                               int ndir, float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream);
-/* nn.LSTM(bidirectional) over packed sequences (instruction_encoder.py:84-94): gx_* = W_ih x + b_ih
- * for all (b,t) as (B*L, 4H); out (B, 2H, L), zero for t >= lengths[b].  H must be 128. */
-int ivln_lstm_bidir_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                            const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                            float* out, float* save_gates, float* save_c, void* stream);
-/* The same recurrence launched with 2B * spare blocks for its 2B (sequence, direction) items: a block takes the next item
- * when it STARTS (atomic ticket in *ticket, a zeroed u32 the caller owns; the last block re-arms it), blocks past 2B
- * leave.  For a replay beside a kernel that saturates some XCDs (ivln_depth_net_f32 with fewer than 8 images): the blocks on
- * the free XCDs do all the work instead of half of it waiting for the neighbour to end.  Same results as the plain entry
- * point for every item; spare 1..8; one launch in flight per ticket word. */
-int ivln_lstm_bidir_fwd_spread_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                                   const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                                   float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, void* stream);
-/* ... and with the per-row cache of ivln_embed_gates_cached_f32: `dirty` i32 (B) or NULL; the (sequence, direction) items
- * of a row with dirty == 0 are not run and `out` keeps that row's values of the last step it was run. */
-int ivln_lstm_bidir_fwd_cached_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                                   const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                                   float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty,
-                                   void* stream);
-/* The same recurrence for `bidirectional` True or False (instruction_encoder.py:27-32, 49: the output width is
- * hidden_size * (1 + bidirectional)): ndir in {1, 2} sets the grid (ndir * B items), out (B, ndir*H, L) and the saves
- * save_gates (B, ndir, L, 4H) / save_c (B, ndir, L, H).  With ndir == 1 the *_r pointers are ignored (may be NULL).
- * ticket / spare / dirty as above (NULL, 1, NULL = the plain launch).  ivln_lstm_bidir_fwd_* are this with ndir = 2. */
+/* nn.LSTM(E, H, bidirectional = ndir == 2) over pack_padded_sequence, then pad_packed_sequence(...).permute(0, 2, 1)
+ * (instruction_encoder.py:27-32, 49, 84-94; csrc/instr_rnn.hip k_lstm_bidir).  H must be 128 (else IVLN_E_UNSUPPORTED).
+ *   gx_*         (B*L, 4H) = W_ih x + b_ih of all positions, torch's gate order i, f, g, o
+ *   whh_*, bhh_* (4H, H), (4H).  With ndir == 1 every *_r pointer is ignored (may be NULL)
+ *   lengths      i32 (B); a sequence runs min(max(lengths[b], 0), L) steps, the reverse direction t = len-1 .. 0
+ *   out          (B, ndir*H, L), exactly zero for t >= that length
+ *   save_gates, save_c  optional, for the BPTT: the activated gates (B, ndir, L, 4H) and cell states (B, ndir, L, H);
+ *                positions t >= length are not written
+ *   ticket, spare  the over-subscribed launch: ticket NULL and spare 1 = the plain launch of ndir * B blocks, block i runs
+ *                item i (item = dir * B + b).  With a ticket (a zeroed u32 the caller owns; one launch in flight per word)
+ *                ndir * B * spare blocks are launched and a block takes the next item when it STARTS (atomic counter in
+ *                *ticket, which the last block re-arms to 0); blocks past the last item leave.  For a replay beside a kernel
+ *                that saturates some XCDs (ivln_depth_net_f32 with fewer than 8 images): the blocks on the free XCDs do all
+ *                the work instead of half of it waiting for the neighbour to end.  Same results for every item.  spare
+ *                1..8; spare > 1 without a ticket is IVLN_E_INVALID
+ *   dirty        i32 (B) or NULL: the flags ivln_embed_gates_dirs_f32 wrote.  The items of a row with dirty == 0 are not
+ *                run and `out` keeps that row's values of the last step it was run (so `out` is a persistent buffer) */
 int ivln_lstm_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
                            const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out,
                            float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty, void* stream);
@@ -550,22 +544,18 @@ int ivln_lstm_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* wh
  * bhh_* (3H), lengths i32 (B); torch's gate order r, z, n and n = tanh(gi_n + r * (W_hn h + b_hn)),
  * h' = (1 - z) * n + z * h.  out (B, ndir*H, L), exactly zero for t >= min(lengths[b], L); the reverse direction runs
  * t = len-1 .. 0; a length of 0 leaves zeros.  save (optional, BPTT) (B, ndir, L, 4, H): r, z, n, W_hn h + b_hn.  dirty i32 (B)
- * or NULL as in ivln_lstm_bidir_fwd_cached_f32: rows with dirty == 0 are not run and `out` keeps their values.  With
- * ndir == 1 the *_r pointers are ignored.  H must be 128 (else IVLN_E_UNSUPPORTED).  A plain launch: no ticket / spare form. */
+ * or NULL, the flags ivln_embed_gates_dirs_f32 wrote: rows with dirty == 0 are not run and `out` keeps their values of the
+ * last step they were run.  With ndir == 1 the *_r pointers are ignored.  H must be 128 (else IVLN_E_UNSUPPORTED).  A plain
+ * launch of ndir * B blocks: no ticket / spare form. */
 int ivln_gru_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
                           const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out, float* save,
                           const int* dirty, void* stream);
-/* (The BPTT of the two entry points above is declared beside them: the instruction encoder's options as one group; their
- * per-kernel tests are tests/test_gpu_instruction_options.py.)
- * BPTT of ivln_lstm_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd): dout / out (B, ndir*H, L), saves as
- * the forward wrote them; with ndir == 1 the *_r pointers are ignored.  ivln_lstm_bidir_bwd_f32 is this with ndir = 2. */
-int ivln_lstm_dirs_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs, const float* whh_f,
-                           const float* whh_r, const int* lengths, int B, int L, int H, int ndir, float* dgx_f, float* dgx_r,
-                           float* hprev_f, float* hprev_r, void* stream);
-/* BPTT of ivln_gru_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd): dout (B, ndir*H, L), `save` and `out`
- * of the forward -> per direction dgi (B*L, 3H), the gradient of W_ih x + b_ih (feeds W_ih, b_ih, the embedding), dgh
- * (B*L, 3H), the gradient of W_hh h + b_hh (its n rows carry the factor r; feeds W_hh, b_hh), hprev (B*L, H) = h_{t-1} in
- * processing order.  All three exactly zero for t >= min(lengths[b], L); dout there is not read.  H must be 128. */
+/* BPTT of ivln_gru_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd), declared beside its forward; its
+ * per-kernel test is in tests/test_gpu_instruction_options.py.  dout (B, ndir*H, L), `save` and `out` of the forward -> per
+ * direction dgi (B*L, 3H), the gradient of W_ih x + b_ih (feeds W_ih, b_ih, the embedding), dgh (B*L, 3H), the gradient of
+ * W_hh h + b_hh (its n rows carry the factor r; feeds W_hh, b_hh), hprev (B*L, H) = h_{t-1} in processing order.  All three
+ * exactly zero for t >= min(lengths[b], L); dout there is not read.  With ndir == 1 the *_r pointers are ignored.  H must be
+ * 128. */
 int ivln_gru_dirs_bwd_f32(const float* dout, const float* out, const float* save, const float* whh_f, const float* whh_r,
                           const int* lengths, int B, int L, int H, int ndir, float* dgi_f, float* dgi_r, float* dgh_f,
                           float* dgh_r, float* hprev_f, float* hprev_r, void* stream);
@@ -824,10 +814,15 @@ int ivln_cma_seq_bwd_f32(const float* d_out, int64_t ld_dout, const float* r, co
 int ivln_linear_skinny_ex_f32(const float* x, int64_t ldx, const float* W, const float* add, int64_t ld_add,
                               const uint8_t* rowmask, float* y, int64_t ldy, int rows, int K, int O,
                               void* stream);
-/* BPTT of ivln_lstm_bidir_fwd_f32: dout (B,2H,L) -> dgx_* (B*L,4H), hprev_* (B*L,H) */
-int ivln_lstm_bidir_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs,
-                            const float* whh_f, const float* whh_r, const int* lengths, int B, int L, int H,
-                            float* dgx_f, float* dgx_r, float* hprev_f, float* hprev_r, void* stream);
+/* BPTT of ivln_lstm_dirs_fwd_f32 (instruction_encoder.py:27-32, 84-94 under autograd; csrc/instr_rnn.hip
+ * k_lstm_bidir_bwd).  dout / out (B, ndir*H, L): the gradient of the forward's output and that output; gates (B, ndir, L, 4H)
+ * and cs (B, ndir, L, H) as the forward saved them; whh_* (4H, H); lengths i32 (B) -> per direction dgx (B*L, 4H), the
+ * gradient of W_ih x + b_ih and of W_hh h + b_hh alike (feeds both weight GEMMs, the biases and the embedding), and hprev
+ * (B*L, H) = h_{t-1} in processing order.  Both exactly zero for t >= min(max(lengths[b], 0), L); dout there is not read.
+ * With ndir == 1 the *_r pointers are ignored (may be NULL).  H must be 128 (else IVLN_E_UNSUPPORTED). */
+int ivln_lstm_dirs_bwd_f32(const float* dout, const float* out, const float* gates, const float* cs, const float* whh_f,
+                           const float* whh_r, const int* lengths, int B, int L, int H, int ndir, float* dgx_f, float* dgx_r,
+                           float* hprev_f, float* hprev_r, void* stream);
 /* backward of BatchNorm2d(train|eval) -> ReLU -> AvgPool2d(2) (CBRA, map_encoder.py:13-20).  ws: scratch of at least
  * 4 * C + 2 floats (the per-channel sums are accumulated and merged in double: 4 floats per (channel, split)). */
 int ivln_cbra_bwd_f32(const float* dout, const float* y, const float* scale, const float* shift,

@@ -667,153 +667,6 @@ __global__ __launch_bounds__(1024) void k_embed_gates(const int64_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// Bidirectional LSTM recurrence (nn.LSTM over a packed sequence, instruction_encoder.py:84-94).
-// grid (B, 2): one block per (sequence, direction); 4H = 512 threads, thread g owns gate row g of
-// W_hh (H=128 weights in registers); h and c live in LDS.  gx = W_ih x + b_ih precomputed by the
-// GEMM for all (b,t).  Gate order i,f,g,o.  out: (B, 2H, L) channel-major, zero for t >= len.
-// Optional saves for BPTT: gates (B,2,L,4H) post-activation, cs (B,2,L,H).
-// ------------------------------------------------------------------------------------------
-// DPP quad permutation of a float (ctrl = p0 | p1<<2 | p2<<4 | p3<<6: lane i of each quad reads lane p_i)
-template <int CTRL>
-__device__ __forceinline__ float quad_perm(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
-// Barrier that orders LDS traffic only.  __syncthreads() also releases GLOBAL stores, i.e. the compiler
-// puts s_waitcnt vmcnt(0) in front of it: in a per-timestep loop that also writes its outputs to HBM
-// every step then waits for the store acknowledgement.  Nothing in those loops reads global data written
-// by the block, so the recurrent kernels order only their LDS traffic.
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// ND = direction count (instruction_encoder.py:27-32, `bidirectional`): the grid is ND * B items, out is (B, ND*H, L) and
-// the saves are (B, ND, L, .); with ND == 1 every item is a forward one and the *_r pointers are never read.
-template <int H, int ND>
-__global__ __launch_bounds__(4 * H) void k_lstm_bidir(const float* __restrict__ gx_f,
-                                                      const float* __restrict__ gx_r,
-                                                      const float* __restrict__ whh_f,
-                                                      const float* __restrict__ whh_r,
-                                                      const float* __restrict__ bhh_f,
-                                                      const float* __restrict__ bhh_r,
-                                                      const int* __restrict__ lengths, int L,
-                                                      float* __restrict__ out, float* __restrict__ save_gates,
-                                                      float* __restrict__ save_c, int B, unsigned* __restrict__ ticket,
-                                                      const int* __restrict__ dirty) {
-    constexpr int G = 4 * H;
-    // Which (sequence, direction) this block runs: its index, or - with `ticket` - the order in which the blocks START.
-    // The launcher then over-subscribes the grid (2B * spare blocks for 2B items): beside a kernel that fills some XCDs
-    // (the persistent depth encoder; this kernel's 340 registers per SIMD lane do not fit next to it) the blocks the
-    // dispatcher handed to the free XCDs start first and take all the work, the others start when the neighbour ends and
-    // leave at once.  The block that draws the last ticket re-arms the counter for the next launch.
-    __shared__ int s_item;
-    int item = blockIdx.x;
-    if (ticket) {
-        if (threadIdx.x == 0) {
-            const unsigned t = atomicAdd(ticket, 1u);
-            if (t == gridDim.x - 1) atomicExch(ticket, 0u);
-            s_item = (int)t;
-        }
-        __syncthreads();
-        item = s_item;
-        if (item >= ND * B) return;
-    }
-    if (dirty && !dirty[item % B]) return;  // (per-episode cache, k_embed_gates: this row's output of last step stands)
-    // Quad j (threads 4j..4j+3) owns hidden unit j: lane q multiplies the 4 gate rows {i,f,g,o} of unit j
-    // with ITS quarter of h (a 4 x H/4 block of W_hh = H weights in registers), the quad adds the partial
-    // sums by DPP, lane q activates gate q, the quad exchanges the four activations by DPP and every lane
-    // updates c/h redundantly (c lives in a register).  Per timestep: H/16 ds_read_b128 per thread (every
-    // thread reading all of h saturated the LDS port), no LDS round trip for gates or cell state and ONE
-    // barrier (h for the next step).
-    constexpr int HQ = H / 4, HQP = HQ + 4;  // +4 words per quarter: the 4 quarters hit different banks
-    __shared__ __attribute__((aligned(16))) float hs[2][4 * HQP];  // double-buffered: one barrier per step
-    const int b = item % B, dir = item / B, tid = threadIdx.x;
-    const int q = tid & 3, j = tid >> 2;
-    const int g = q * H + j;  // this lane's gate row (PyTorch order i,f,g,o)
-    const float* gx = (dir == 0 ? gx_f : gx_r) + (int64_t)b * L * G;
-    const float* whh = (dir == 0 ? whh_f : whh_r);
-    const float bias = (dir == 0 ? bhh_f : bhh_r)[g];
-    v2f w[4][HQ / 2];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int k = 0; k < HQ / 2; ++k) {
-            const float* wp = whh + (int64_t)(r * H + j) * H + q * HQ + 2 * k;
-            w[r][k] = v2f{wp[0], wp[1]};
-        }
-    const int hslot = (j / HQ) * HQP + j % HQ;
-    if (q == 0) hs[0][hslot] = 0.f;
-    float c = 0.f;
-    lds_barrier();
-    int len = lengths[b];
-    if (len > L) len = L;
-    // gx (this lane's gate input, one float per timestep) is prefetched FOUR steps ahead in a rotating
-    // register queue: a timestep is ~0.4 us of work but a fresh HBM row costs ~2 us, so a one-step
-    // prefetch left every step waiting on memory.
-    auto gx_at = [&](int s) -> float {
-        return s < len ? gx[(int64_t)(dir == 0 ? s : len - 1 - s) * G + g] : 0.f;
-    };
-    auto step = [&](int s, float gxv) {
-        const int t = dir == 0 ? s : len - 1 - s;
-        const float* hcur = hs[s & 1];
-        v2f p[4] = {v2f{0.f, 0.f}, v2f{0.f, 0.f}, v2f{0.f, 0.f}, v2f{0.f, 0.f}};
-#pragma unroll
-        for (int k = 0; k < HQ; k += 4) {
-            const float4 hv = *reinterpret_cast<const float4*>(&hcur[q * HQP + k]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                p[r] = __builtin_elementwise_fma(w[r][k / 2], v2f{hv.x, hv.y}, p[r]);
-                p[r] = __builtin_elementwise_fma(w[r][k / 2 + 1], v2f{hv.z, hv.w}, p[r]);
-            }
-        }
-        float ps[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = p[r].x + p[r].y;
-            v += quad_perm<0xB1>(v);  // lanes 1,0,3,2
-            v += quad_perm<0x4E>(v);  // lanes 2,3,0,1
-            ps[r] = v;
-        }
-        const float acc = gxv + bias + (q == 0 ? ps[0] : (q == 1 ? ps[1] : (q == 2 ? ps[2] : ps[3])));
-        // sigmoid / tanh through one fast exp each (|err| ~1e-7): tanh(x) = 2*sigmoid(2x) - 1
-        // (v_rcp_f32 is 1 ulp; an IEEE division is a ~10-instruction sequence on the per-step critical path)
-        const float e = __expf(q == 2 ? -2.f * acc : -acc);
-        const float rc = __builtin_amdgcn_rcpf(1.f + e);
-        const float a = q == 2 ? 2.f * rc - 1.f : rc;
-        if (save_gates) save_gates[(((int64_t)b * ND + dir) * L + t) * G + g] = a;
-        const float ai = quad_perm<0x00>(a), af = quad_perm<0x55>(a), ag = quad_perm<0xAA>(a), ao = quad_perm<0xFF>(a);
-        c = af * c + ai * ag;
-        const float h = ao * (2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * c)) - 1.f);
-        if (q == 0) {
-            hs[(s + 1) & 1][hslot] = h;
-            out[((int64_t)b * ND * H + dir * H + j) * L + t] = h;
-            if (save_c) save_c[(((int64_t)b * ND + dir) * L + t) * H + j] = c;
-        }
-        lds_barrier();
-    };
-    float g0 = gx_at(0), g1 = gx_at(1), g2 = gx_at(2), g3 = gx_at(3);
-    for (int s = 0; s < len; s += 4) {
-        step(s, g0);
-        g0 = gx_at(s + 4);
-        if (s + 1 >= len) break;
-        step(s + 1, g1);
-        g1 = gx_at(s + 5);
-        if (s + 2 >= len) break;
-        step(s + 2, g2);
-        g2 = gx_at(s + 6);
-        if (s + 3 >= len) break;
-        step(s + 3, g3);
-        g3 = gx_at(s + 7);
-    }
-    if (q == 0)
-        for (int t = len; t < L; ++t) out[((int64_t)b * ND * H + dir * H + j) * L + t] = 0.f;
-}
-
-// ------------------------------------------------------------------------------------------
 // Skinny linear: y[n][o] = act(W[o].x[n] + b[o]) for few rows n (rollout batch).  One 256-thread
 // block per output row: the 4 waves split K (float4 loads, every lane busy even at K = 3072),
 // partial sums meet in LDS.  Rows processed 8 at a time.
@@ -1636,16 +1489,6 @@ int ivln_embed_lengths(const int64_t* tokens, const float* table, int B, int L, 
     return LAUNCH_OK();
 }
 
-int ivln_embed_gates_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
-                         float* gx_f, float* gx_r, int* lengths, void* stream) {
-    return ivln_embed_gates_cached_f32(tokens, table, row_nonzero, B, L, G, V, gx_f, gx_r, lengths, nullptr, nullptr, stream);
-}
-
-int ivln_embed_gates_cached_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
-                                float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream) {
-    return ivln_embed_gates_dirs_f32(tokens, table, row_nonzero, B, L, G, V, 2, gx_f, gx_r, lengths, cache_tokens, dirty, stream);
-}
-
 int ivln_embed_gates_dirs_f32(const int64_t* tokens, const float* table, const uint8_t* row_nonzero, int B, int L, int G, int V,
                               int ndir, float* gx_f, float* gx_r, int* lengths, int64_t* cache_tokens, int* dirty, void* stream) {
     if (!tokens || !table || !row_nonzero || !gx_f || !lengths || B <= 0 || L <= 0 || G <= 0 || (G & 3) || V <= 0)
@@ -1658,43 +1501,6 @@ int ivln_embed_gates_dirs_f32(const int64_t* tokens, const float* table, const u
     else  // one direction: table (V, G)
         hipLaunchKernelGGL(k_embed_gates<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, tokens, table, row_nonzero, L, G, V,
                            gx_f, gx_r, lengths, cache_tokens, dirty);
-    return LAUNCH_OK();
-}
-
-int ivln_lstm_bidir_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                            const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                            float* out, float* save_gates, float* save_c, void* stream) {
-    return ivln_lstm_bidir_fwd_cached_f32(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, out, save_gates, save_c,
-                                          nullptr, 1, nullptr, stream);
-}
-
-int ivln_lstm_bidir_fwd_spread_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                                   const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                                   float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, void* stream) {
-    return ivln_lstm_bidir_fwd_cached_f32(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, out, save_gates, save_c,
-                                          ticket, spare, nullptr, stream);
-}
-
-int ivln_lstm_bidir_fwd_cached_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
-                                   const float* bhh_f, const float* bhh_r, const int* lengths, int B, int L, int H,
-                                   float* out, float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty,
-                                   void* stream) {
-    return ivln_lstm_dirs_fwd_f32(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, 2, out, save_gates, save_c, ticket,
-                                  spare, dirty, stream);
-}
-
-int ivln_lstm_dirs_fwd_f32(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bhh_f,
-                           const float* bhh_r, const int* lengths, int B, int L, int H, int ndir, float* out,
-                           float* save_gates, float* save_c, unsigned* ticket, int spare, const int* dirty, void* stream) {
-    if (H != 128) return IVLN_E_UNSUPPORTED;
-    if (B <= 0 || L <= 0 || spare < 1 || spare > 8 || (spare > 1 && !ticket) || (ndir != 1 && ndir != 2)) return IVLN_E_INVALID;
-    if (!gx_f || !whh_f || !bhh_f || !lengths || !out || (ndir == 2 && (!gx_r || !whh_r || !bhh_r))) return IVLN_E_INVALID;
-    if (ndir == 2)
-        hipLaunchKernelGGL((k_lstm_bidir<128, 2>), dim3(2 * B * (ticket ? spare : 1)), dim3(512), 0, (hipStream_t)stream, gx_f,
-                           gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, L, out, save_gates, save_c, B, ticket, dirty);
-    else
-        hipLaunchKernelGGL((k_lstm_bidir<128, 1>), dim3(B * (ticket ? spare : 1)), dim3(512), 0, (hipStream_t)stream, gx_f,
-                           gx_f, whh_f, whh_f, bhh_f, bhh_f, lengths, L, out, save_gates, save_c, B, ticket, dirty);
     return LAUNCH_OK();
 }
 

@@ -208,7 +208,7 @@ class InstructionEncoder(nn.Module):
             return torch.tensor(json.load(f))
 
     def _gate_table(self):
-        """(table (V, ndir * gates * H), row_nonzero u8 (V)) of ivln_embed_gates_f32, cached until a weight changes; None
+        """(table (V, ndir * gates * H), row_nonzero u8 (V)) of ivln_embed_gates_dirs_f32, cached until a weight changes; None
         while a stream capture is running and no valid table exists (the caller then runs the unfolded launches)."""
         E = self.embedding_layer.weight
         ws, bs = self.dir_params("weight_ih"), self.dir_params("bias_ih")

@@ -126,7 +126,9 @@ def _L():
         L.ivln_pool2d_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.ivln_map_features_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.ivln_embed_lengths.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-        L.ivln_lstm_bidir_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, vp, vp, vp, vp]
+        L.ivln_embed_gates_dirs_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.ivln_lstm_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+        L.ivln_gru_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp]
         L.ivln_linear_skinny_f32.argtypes = [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]
         L.ivln_gru_step_f32.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32,
                                         vp, vp, vp, vp, vp]
@@ -1246,14 +1248,13 @@ def embed_lengths(tokens_i64, table):
 
 
 def embed_gates(tokens_i64, table, row_nonzero, cache=None, ndir=2):
-    """tokens (B, L) -> gx_f, gx_r (B*L, G) looked up in the folded (V, ndir*G) table, lengths i32 (B) (k_embed_gates).
-    cache: an `InstructionStepCache` - its persistent gx / lengths buffers are the outputs and only the rows whose tokens
-    differ from the cached ones are written (ivln_embed_gates_cached_f32; cache.dirty says which).
-    ndir=1: a unidirectional encoder (ivln_embed_gates_dirs_f32) - table (V, G), gx_r is None."""
+    """tokens (B, L) -> gx_f, gx_r (B*L, G) looked up in the folded (V, ndir*G) table, lengths i32 (B)
+    (ivln_embed_gates_dirs_f32, k_embed_gates).  cache: an `InstructionStepCache` - its persistent gx / lengths buffers are
+    the outputs and only the rows whose tokens differ from the cached ones are written (cache.dirty says which).
+    ndir=1: a unidirectional encoder - table (V, G), gx_r is None."""
     B, L = tokens_i64.shape
     V, G2 = table.shape
     G = G2 // ndir
-    Lb = _L()
     if cache is not None:
         gx_f, gx_r, lengths = cache.gx_f, cache.gx_r, cache.lengths
         ct, dirty = dptr(cache.tokens), dptr(cache.dirty)
@@ -1262,15 +1263,8 @@ def embed_gates(tokens_i64, table, row_nonzero, cache=None, ndir=2):
         gx_r = torch.empty((B * L, G), dtype=torch.float32, device=table.device) if ndir == 2 else None
         lengths = torch.empty((B,), dtype=torch.int32, device=table.device)
         ct = dirty = None
-    if ndir == 2:
-        Lb.ivln_embed_gates_cached_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        check(Lb.ivln_embed_gates_cached_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, dptr(gx_f), dptr(gx_r),
-                                             dptr(lengths), ct, dirty, stream_ptr()),
-              "ivln_embed_gates_cached_f32" if cache is not None else "ivln_embed_gates_f32")
-    else:
-        Lb.ivln_embed_gates_dirs_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        check(Lb.ivln_embed_gates_dirs_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, ndir, dptr(gx_f),
-                                           _p(gx_r), dptr(lengths), ct, dirty, stream_ptr()), "ivln_embed_gates_dirs_f32")
+    check(_L().ivln_embed_gates_dirs_f32(dptr(tokens_i64), dptr(table), dptr(row_nonzero), B, L, G, V, ndir, dptr(gx_f),
+                                         _p(gx_r), dptr(lengths), ct, dirty, stream_ptr()), "ivln_embed_gates_dirs_f32")
     return gx_f, gx_r, lengths
 
 
@@ -1312,8 +1306,14 @@ def invalidate_step_caches():
         c.invalidate()
 
 
-def _lstm_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir, save, spare, ticket, cache):
-    """ivln_lstm_dirs_fwd_f32: the recurrence with a direction count (lstm_bidir's body for ndir != 2)."""
+def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=False, spare=1, ticket=None, cache=None,
+               ndir=2):
+    """nn.LSTM over packed sequences, ndir directions (ivln_lstm_dirs_fwd_f32): gx_* (B*L, 4H) -> out (B, ndir*H, L), zero
+    beyond each length; gates (B, ndir, L, 4H) and cs (B, ndir, L, H) when `save`, else None.  ndir=1: the *_r arguments are
+    None.  spare > 1 (without `save`): ndir * B * spare blocks draw the ndir * B items in the order they start (for a replay
+    beside a launch that fills some XCDs).  ticket: the caller's zeroed int32 word (one launch in flight per word).
+    cache (without `save`): the step cache whose `dirty` flags `embed_gates` just wrote - rows with dirty == 0 are not run
+    and cache.out (the returned tensor) keeps their values."""
     dev = gx_f.device
     tk = ticket if spare > 1 and not save else None
     if spare > 1 and not save and (tk is None or tk.dtype != torch.int32 or tk.device != dev):
@@ -1324,54 +1324,9 @@ def _lstm_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir, s
     if save:
         gates = torch.zeros((B, ndir, L, 4 * H), dtype=torch.float32, device=dev)
         cs = torch.zeros((B, ndir, L, H), dtype=torch.float32, device=dev)
-    Lb = _L()
-    Lb.ivln_lstm_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
-    check(Lb.ivln_lstm_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L,
-                                    H, ndir, dptr(out), _p(gates), _p(cs), _p(tk), int(spare) if tk is not None else 1,
-                                    dptr(cache.dirty) if cached else None, stream_ptr()), "ivln_lstm_dirs_fwd_f32")
-    return out, gates, cs
-
-
-def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=False, spare=1, ticket=None, cache=None,
-               ndir=2):
-    """ndir=1: one direction (the *_r arguments are None), out (B, H, L), saves (B, 1, L, .).
-    spare > 1: ivln_lstm_bidir_fwd_spread_f32 - 2B * spare blocks draw the 2B items in the order they start (for a
-    replay beside a launch that fills some XCDs).  ticket: the caller's zeroed int32 word (one launch in flight per word).
-    cache: the step cache whose `dirty` flags `embed_gates` just wrote - rows with dirty == 0 are not run and cache.out
-    (the returned tensor) keeps their values."""
-    if ndir != 2:
-        return _lstm_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir, save, spare, ticket, cache)
-    if cache is not None and not save:
-        tk = ticket if spare > 1 else None
-        if spare > 1 and (tk is None or tk.dtype != torch.int32 or tk.device != gx_f.device):
-            raise ValueError("lstm_bidir(spare>1) needs the caller's int32 ticket word on the same device")
-        Lb = _L()
-        Lb.ivln_lstm_bidir_fwd_cached_f32.argtypes = [vp] * 7 + [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
-        check(Lb.ivln_lstm_bidir_fwd_cached_f32(dptr(gx_f), dptr(gx_r), dptr(whh_f), dptr(whh_r), dptr(bhh_f), dptr(bhh_r),
-                                                dptr(lengths), B, L, H, dptr(cache.out), None, None, _p(tk),
-                                                int(spare) if tk is not None else 1, dptr(cache.dirty), stream_ptr()),
-              "ivln_lstm_bidir_fwd_cached_f32")
-        return cache.out, None, None
-    out = torch.empty((B, 2 * H, L), dtype=torch.float32, device=gx_f.device)
-    if spare > 1 and not save:
-        tk = ticket
-        if tk is None or tk.dtype != torch.int32 or tk.device != gx_f.device:
-            raise ValueError("lstm_bidir(spare>1) needs the caller's int32 ticket word on the same device")
-        Lb = _L()
-        Lb.ivln_lstm_bidir_fwd_spread_f32.argtypes = [vp] * 7 + [i32, i32, i32, vp, vp, vp, vp, i32, vp]
-        check(Lb.ivln_lstm_bidir_fwd_spread_f32(dptr(gx_f), dptr(gx_r), dptr(whh_f), dptr(whh_r), dptr(bhh_f), dptr(bhh_r),
-                                                dptr(lengths), B, L, H, dptr(out), None, None, dptr(tk), int(spare),
-                                                stream_ptr()), "ivln_lstm_bidir_fwd_spread_f32")
-        return out, None, None
-    gates = cs = None
-    if save:
-        gates = torch.zeros((B, 2, L, 4 * H), dtype=torch.float32, device=gx_f.device)
-        cs = torch.zeros((B, 2, L, H), dtype=torch.float32, device=gx_f.device)
-    check(
-        _L().ivln_lstm_bidir_fwd_f32(dptr(gx_f), dptr(gx_r), dptr(whh_f), dptr(whh_r), dptr(bhh_f), dptr(bhh_r),
-                                     dptr(lengths), B, L, H, dptr(out), _p(gates), _p(cs), stream_ptr()),
-        "ivln_lstm_bidir_fwd_f32",
-    )
+    check(_L().ivln_lstm_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L,
+                                      H, ndir, dptr(out), _p(gates), _p(cs), _p(tk), int(spare) if tk is not None else 1,
+                                      dptr(cache.dirty) if cached else None, stream_ptr()), "ivln_lstm_dirs_fwd_f32")
     return out, gates, cs
 
 
@@ -1383,10 +1338,8 @@ def gru_dirs(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, ndir=2, s
     cached = cache is not None and not save
     out = cache.out if cached else torch.empty((B, ndir * H, L), dtype=torch.float32, device=dev)
     saves = torch.zeros((B, ndir, L, 4, H), dtype=torch.float32, device=dev) if save else None
-    Lb = _L()
-    Lb.ivln_gru_dirs_fwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp]
-    check(Lb.ivln_gru_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L, H,
-                                   ndir, dptr(out), _p(saves), dptr(cache.dirty) if cached else None, stream_ptr()),
+    check(_L().ivln_gru_dirs_fwd_f32(dptr(gx_f), _p(gx_r), dptr(whh_f), _p(whh_r), dptr(bhh_f), _p(bhh_r), dptr(lengths), B, L,
+                                     H, ndir, dptr(out), _p(saves), dptr(cache.dirty) if cached else None, stream_ptr()),
           "ivln_gru_dirs_fwd_f32")
     return out, saves
 
@@ -1754,7 +1707,7 @@ def copy2d(src, dst, rows, cols, broadcast_rows=False):
     )
 
 
-# ---- backward / loss / optimizer bindings (csrc/train_ops.hip) -------------------------------------
+# ---- backward / loss / optimizer bindings (csrc/train_ops.hip, csrc/instr_rnn.hip) ----------------
 _tsigs_done = False
 
 
@@ -1772,7 +1725,8 @@ def _T():
                                         i64, vp, i64, vp]
         L.ivln_gru_bwd_elem_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp]
         L.ivln_linear_skinny_ex_f32.argtypes = [vp, i64, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]
-        L.ivln_lstm_bidir_bwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, vp, vp, vp, vp, vp]
+        L.ivln_lstm_dirs_bwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.ivln_gru_dirs_bwd_f32.argtypes = [vp] * 6 + [i32, i32, i32, i32] + [vp] * 7
         L.ivln_cbra_bwd_f32.argtypes = [vp] * 6 + [i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
         L.ivln_embedding_scatter_add_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
         L.ivln_prev_action_embed_bwd_f32.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, i32, vp, vp]
@@ -1962,42 +1916,22 @@ def gru_dirs_bwd(dout, out, saves, whh_f, whh_r, lengths, B, L, H, ndir=2):
     dev = dout.device
     res = [tuple(torch.empty((B * L, w), dtype=torch.float32, device=dev) for w in (3 * H, 3 * H, H)) for _ in range(ndir)]
     f, r = res[0], (res[1] if ndir == 2 else (None, None, None))
-    Lb = _T()
-    Lb.ivln_gru_dirs_bwd_f32.argtypes = [vp] * 6 + [i32, i32, i32, i32] + [vp] * 7
-    check(Lb.ivln_gru_dirs_bwd_f32(dptr(dout), dptr(out), dptr(saves), dptr(whh_f), _p(whh_r), dptr(lengths), B, L, H, ndir,
-                                   dptr(f[0]), _p(r[0]), dptr(f[1]), _p(r[1]), dptr(f[2]), _p(r[2]), stream_ptr()),
+    check(_T().ivln_gru_dirs_bwd_f32(dptr(dout), dptr(out), dptr(saves), dptr(whh_f), _p(whh_r), dptr(lengths), B, L, H, ndir,
+                                     dptr(f[0]), _p(r[0]), dptr(f[1]), _p(r[1]), dptr(f[2]), _p(r[2]), stream_ptr()),
           "ivln_gru_dirs_bwd_f32")
     return res
 
 
-def _lstm_dirs_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir):
-    """ivln_lstm_dirs_bwd_f32: the BPTT with a direction count (lstm_bidir_bwd's body for ndir != 2)."""
+def lstm_bidir_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir=2):
+    """BPTT of lstm_bidir (ivln_lstm_dirs_bwd_f32) -> dgx_f, dgx_r (B*L, 4H), hp_f, hp_r (B*L, H), zero at padded
+    positions.  ndir=1: one direction (whh_r None) -> dgx_r / hp_r are None."""
     dev = dout.device
     dgx = [torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev) for _ in range(ndir)] + [None]
     hp = [torch.empty((B * L, H), dtype=torch.float32, device=dev) for _ in range(ndir)] + [None]
-    Lb = _T()
-    Lb.ivln_lstm_dirs_bwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    check(Lb.ivln_lstm_dirs_bwd_f32(dptr(dout), dptr(out), dptr(gates), dptr(cs), dptr(whh_f), _p(whh_r), dptr(lengths), B, L, H,
-                                    ndir, dptr(dgx[0]), _p(dgx[1]), dptr(hp[0]), _p(hp[1]), stream_ptr()), "ivln_lstm_dirs_bwd_f32")
+    check(_T().ivln_lstm_dirs_bwd_f32(dptr(dout), dptr(out), dptr(gates), dptr(cs), dptr(whh_f), _p(whh_r), dptr(lengths), B, L,
+                                      H, ndir, dptr(dgx[0]), _p(dgx[1]), dptr(hp[0]), _p(hp[1]), stream_ptr()),
+          "ivln_lstm_dirs_bwd_f32")
     return dgx[0], dgx[1], hp[0], hp[1]
-
-
-def lstm_bidir_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir=2):
-    """ndir=1: one direction (whh_r None) -> dgx_r / hp_r are None."""
-    if ndir != 2:
-        return _lstm_dirs_bwd(dout, out, gates, cs, whh_f, whh_r, lengths, B, L, H, ndir)
-    dev = dout.device
-    dgx_f = torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev)
-    dgx_r = torch.empty((B * L, 4 * H), dtype=torch.float32, device=dev)
-    hp_f = torch.empty((B * L, H), dtype=torch.float32, device=dev)
-    hp_r = torch.empty((B * L, H), dtype=torch.float32, device=dev)
-    check(
-        _T().ivln_lstm_bidir_bwd_f32(dptr(dout), dptr(out), dptr(gates), dptr(cs), dptr(whh_f), dptr(whh_r),
-                                     dptr(lengths), B, L, H, dptr(dgx_f), dptr(dgx_r), dptr(hp_f), dptr(hp_r),
-                                     stream_ptr()),
-        "ivln_lstm_bidir_bwd_f32",
-    )
-    return dgx_f, dgx_r, hp_f, hp_r
 
 
 def cbra_bwd(dout, y, scale, shift, mean, rstd, train):

@@ -1,9 +1,9 @@
 """GPU: the instruction encoder's options - `MODEL.INSTRUCTION_ENCODER.rnn_type` GRU | LSTM, `bidirectional` True | False
 (instruction_encoder.py:27-32, 49).  The recurrences alone (csrc/instr_rnn.hip k_gru_dirs / k_gru_dirs_bwd, and
 k_lstm_bidir / k_lstm_bidir_bwd with one direction) against float64 torch.nn.GRU / nn.LSTM on packed sequences, the
-bidirectional LSTM byte for byte against the entry points it had, then the MapCMA policy built with every non-default
-combination, and Latent-CMA with (GRU, bidirectional) and (LSTM, unidirectional): rollout step, distribution over T = 3,
-one update's gradients, hipGraph replay.
+LSTM's launch forms (plain, ticket + spare, step cache) byte for byte against each other, then the MapCMA policy built
+with every non-default combination, and Latent-CMA with (GRU, bidirectional) and (LSTM, unidirectional): rollout step,
+distribution over T = 3, one update's gradients, hipGraph replay.
 
 Bounds (none derived from what the kernels give):
   forward   2e-5 absolute + 1e-4 relative: tests/test_gpu_kernels.py::test_lstm_bidir_matches_packed_torch_lstm (values in [-1, 1])
@@ -168,38 +168,66 @@ def test_gru_refuses_other_hidden_sizes_and_direction_counts():
             ops.gru_dirs(z, z, z, z, z, z, lengths, 1, 1, Hx)
     with pytest.raises(IvlnError, match=r"\(-1\)"):
         ops.gru_dirs(z, z, z, z, z, z, lengths, 1, 1, 128, ndir=3)
-    # the folded front end: the direction count and gx_r must agree, and the two-direction entry point refuses a NULL gx_r
+    # the folded front end: the direction count and gx_r must agree
     tok = torch.zeros(1, 4, dtype=torch.int64, device=DEV)
     nz = torch.ones(8, dtype=torch.uint8, device=DEV)
     ln = torch.zeros(1, dtype=torch.int32, device=DEV)
     Lb, G = ops._L(), 384
     tab, gx = torch.zeros(8, 2 * G, device=DEV), torch.zeros(4, G, device=DEV)
-    ops.embed_gates(tok, tab, nz, ndir=2), ops.embed_gates(tok, tab[:, :G].contiguous(), nz, ndir=1)  # (sets the argtypes)
+    ops.embed_gates(tok, tab, nz, ndir=2), ops.embed_gates(tok, tab[:, :G].contiguous(), nz, ndir=1)
     a = (tok.data_ptr(), tab.data_ptr(), nz.data_ptr(), 1, 4, G, 8)
-    assert Lb.ivln_embed_gates_cached_f32(*a, gx.data_ptr(), None, ln.data_ptr(), None, None, None) == -1
     assert Lb.ivln_embed_gates_dirs_f32(*a, 2, gx.data_ptr(), None, ln.data_ptr(), None, None, None) == -1
     assert Lb.ivln_embed_gates_dirs_f32(*a, 1, gx.data_ptr(), gx.data_ptr(), ln.data_ptr(), None, None, None) == -1
     torch.cuda.synchronize()
 
 
-def test_bidirectional_lstm_is_the_same_bytes_through_the_direction_count_entry_points():
-    """ops.lstm_bidir / lstm_bidir_bwd (the ivln_lstm_bidir_* entry points) and ivln_lstm_dirs_*_f32 with ndir = 2"""
+def test_lstm_is_the_same_bytes_through_every_launch_form():
+    """ivln_lstm_dirs_fwd_f32 launched plain, with a ticket and spare = 3, and with a fresh InstructionStepCache whose rows
+    are all dirty, for two directions and for one: the same bytes (out; gates and cs too where the form saves them), and the
+    BPTT on those saves against the float64 reference.  lens (37, 5, 20, 1): every tail of the four-deep prefetch loop, the
+    reverse direction, and - with the ticket - blocks that leave without work."""
+    for ndir in (2, 1):
+        _lstm_launch_forms(ndir)
+
+
+def _lstm_launch_forms(ndir):
     from ivln_ce_amd import ops
 
     B, L, lens = 4, 37, (37, 5, 20, 1)
-    c = make_case("LSTM", 2, B, L)
+    r = _reference("LSTM", ndir, B, L, lens)
+    c, eff = r["case"], r["eff"]
     lengths = torch.tensor(lens, dtype=torch.int32, device=DEV)
-    d = [t.to(DEV) for k in ("gx", "whh", "bhh") for t in c[k]]
-    old = ops.lstm_bidir(*d, lengths, B, L, H, save=True)
-    assert all(_same_bytes(a, b) for a, b in zip(old, ops.lstm_bidir(*d, lengths, B, L, H, save=True, ndir=2)))
-    new = ops._lstm_dirs(*d, lengths, B, L, H, 2, True, 1, None, None)
-    for name, a, b in zip(("out", "gates", "cs"), old, new):
-        assert _same_bytes(a, b), name
+    d = [t for k in ("gx", "whh", "bhh") for t in ([x.to(DEV) for x in c[k]] + [None])[:2]]
+    plain = ops.lstm_bidir(*d, lengths, B, L, H, save=True, ndir=ndir)
+    for name, a, b_ in zip(("out", "gates", "cs"), plain, ops.lstm_bidir(*d, lengths, B, L, H, save=True, ndir=ndir)):
+        assert _same_bytes(a, b_), f"save=True twice: {name}"
+    out, gates, cs = ops.lstm_bidir(*d, lengths, B, L, H, ndir=ndir)
+    assert gates is None and cs is None and _same_bytes(out, plain[0]), "plain without saves"
+    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for _ in range(2):  # (twice: the re-armed ticket serves the next launch)
+        out, gates, cs = ops.lstm_bidir(*d, lengths, B, L, H, spare=3, ticket=ticket, ndir=ndir)
+        assert gates is None and cs is None and _same_bytes(out, plain[0]), "ticket + spare=3"
+        assert int(ticket.item()) == 0
+    cache = ops.InstructionStepCache(B, L, 4 * H, H, DEV, key=None, ndir=ndir)
+    assert cache.dirty.tolist() == [1] * B
+    cache.out.fill_(7.0)
+    out, gates, cs = ops.lstm_bidir(*d, lengths, B, L, H, cache=cache, ndir=ndir)
+    assert out is cache.out and gates is None and cs is None and _same_bytes(out, plain[0]), "fresh cache, every row dirty"
+    out, _, _ = ops.lstm_bidir(*d, lengths, B, L, H, spare=3, ticket=ticket, cache=cache, ndir=ndir)
+    assert _same_bytes(out, plain[0]) and int(ticket.item()) == 0, "ticket + spare=3 + cache"
+    # the BPTT on the saves of the plain form
     dout = c["dout"].to(DEV)
-    g_old = ops.lstm_bidir_bwd(dout, old[0], old[1], old[2], d[2], d[3], lengths, B, L, H)
-    g_new = ops._lstm_dirs_bwd(dout, new[0], new[1], new[2], d[2], d[3], lengths, B, L, H, 2)
-    for name, a, b in zip(("dgx_f", "dgx_r", "hprev_f", "hprev_r"), g_old, g_new):
-        assert _same_bytes(a, b), name
+    got = _twice(lambda: tuple(t for t in ops.lstm_bidir_bwd(dout, plain[0], plain[1], plain[2], d[2], d[3], lengths, B, L, H,
+                                                             ndir=ndir) if t is not None))
+    per_dir = [dict(dgi=got[k], hp=got[ndir + k]) for k in range(ndir)]
+    pad = torch.tensor([[t >= n for t in range(L)] for n in eff]).view(B * L)
+    bar = _Bar(f"LSTM ndir={ndir} B={B} L={L} lens={lens}")
+    for k, res in enumerate(per_dir):
+        for name, gv in res.items():
+            gv = gv.cpu()
+            assert bool((gv[pad] == 0).all()), f"{name}[{k}]: padded positions are not exactly zero"
+            bar.check(f"{name}[{k}]", gv, r["m64"][name][k], r["m32"][name][k])
+    bar.done()
 
 
 # ------------------------------------------------------------------------------------------------------------------

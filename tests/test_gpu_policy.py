@@ -303,7 +303,7 @@ def test_fused_head_matches_unfused_chain_and_oracle(B, lens):
 
 def test_instruction_front_end_folded_into_a_table_lookup_is_the_same_encoder():
     """Inference fold: embedding lookup + the two W_ih projections of the bi-LSTM = one lookup in
-    table[v] = E[v] . [W_ih ; W_ih_rev]^T + b (ivln_embed_gates_f32).  Same outputs and the same `lengths` as the
+    table[v] = E[v] . [W_ih ; W_ih_rev]^T + b (ivln_embed_gates_dirs_f32).  Same outputs and the same `lengths` as the
     unfolded launches, including the reference's quirk that a token counts only if its EMBEDDING row has a non-zero
     element (instruction_encoder.py:70-78) - rows 0 and 7 of the table are zeroed here - and the table is rebuilt
     when a weight changes."""

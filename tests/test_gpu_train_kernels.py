@@ -620,7 +620,7 @@ def _lstm_ref(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lens, dout, B, L, H, dt):
 
 @pytest.mark.parametrize("B,L,lens", [(1, 1, [1]), (3, 5, [5, 7, 1]), (4, 80, [80, 37, 37, 100]), (3, 5, [3, 0, 5])])
 def test_lstm_bidir_bwd(B, L, lens):
-    """ivln_lstm_bidir_bwd_f32 (forward saves from ops.lstm_bidir(save=True)) against float64 autograd of a packed
+    """ivln_lstm_dirs_bwd_f32 (forward saves from ops.lstm_bidir(save=True)) against float64 autograd of a packed
     torch.nn.LSTM: gradients of the gate pre-activations and h_{t-1} per direction.  Lengths 1, L, beyond L (clamped like
     the forward), two equal ones.  Length 0, which pack_padded_sequence refuses: the forward runs no step and writes zeros,
     the backward's contract is dgx = 0, hprev = 0 for that row - asserted; the reference runs that row with length 1 and
@@ -1099,7 +1099,7 @@ COVERED = {
     "ivln_gru_bwd_step_f32": "test_gru_bptt_kernels",
     "ivln_cma_seq_bwd_f32": "test_gru_bptt_kernels",
     "ivln_linear_skinny_ex_f32": "test_linear_skinny_ex",
-    "ivln_lstm_bidir_bwd_f32": "test_lstm_bidir_bwd",
+    "ivln_lstm_dirs_bwd_f32": "test_lstm_bidir_bwd",
     "ivln_cbra_bwd_f32": "test_cbra_bwd",
     "ivln_embedding_scatter_add_f32": "test_embedding_scatter_add",
     "ivln_prev_action_embed_bwd_f32": "test_prev_action_embed_bwd",

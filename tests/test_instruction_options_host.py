@@ -114,3 +114,22 @@ def test_latent_oracle_of_the_gpu_tests_is_the_reference_at_the_default_combinat
     e_s = float((states - torch.from_numpy(g["rnn_out"])).abs().max())
     print(f"latent oracle vs reference golden: logits {e_l:.3e} states {e_s:.3e} action loss {action_loss:.7f} ref {float(g['action_loss']):.7f}")
     assert e_l < 1e-5 and e_s < 1e-5 and abs(action_loss - float(g["action_loss"])) < 2e-5
+
+
+def test_the_instruction_encoder_has_one_entry_point_per_kernel():
+    """include/ivln_hip.h declares, of the instruction encoder (front end, recurrences, BPTT), exactly the five entry points
+    below and ivln_embed_lengths, each once; no other name of those families - an entry point that forwards to one of them
+    with arguments filled in - is declared or mentioned there, or anywhere in ops.py"""
+    import os
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    keep = ["ivln_embed_gates_dirs_f32", "ivln_embed_lengths", "ivln_gru_dirs_bwd_f32", "ivln_gru_dirs_fwd_f32",
+            "ivln_lstm_dirs_bwd_f32", "ivln_lstm_dirs_fwd_f32"]
+    family = r"\bivln_(?:embed_gates|embed_lengths|lstm_bidir|lstm_dirs|gru_dirs)\w*"
+    header = open(os.path.join(root, "include", "ivln_hip.h")).read()
+    declared = re.findall("(" + family + r")\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    assert sorted(declared) == keep, declared
+    assert sorted(set(re.findall(family, header))) == keep
+    ops_src = open(os.path.join(root, "ivln-ce_amd", "ops.py")).read()
+    assert sorted(set(re.findall(family, ops_src))) == keep
