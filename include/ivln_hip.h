@@ -451,7 +451,9 @@ int ivln_nconv_f32(const ivln_nconv_desc* d, void* stream);
  * compression (reference call site models/encoders/resnet_encoders.py:31-43,95).  *_img_stride = 0
  * -> C*HW.  save_mean/save_rstd (N*groups) optional.  The input may be the split-K workspace of the
  * producing conv (splits slabs of a [C][N*HW] matrix: x_chan_stride = N*HW, x_img_stride = HW,
- * slab_stride = C*N*HW): the slab reduction is fused into the normalisation. */
+ * slab_stride = C*N*HW): the slab reduction is fused into the normalisation.  16-byte accesses are used only when
+ * HW % 4 == 0 and x, y, residual (and x2) and every stride given keep them on 16-byte boundaries; any other view is
+ * read and written 4 bytes at a time (same values). */
 int ivln_groupnorm_f32(const float* x, const float* gamma, const float* beta, const float* residual,
                        float* y, int N, int C, int HW, int groups, float eps, int relu,
                        int64_t x_img_stride, int64_t x_chan_stride, int splits, int64_t slab_stride,
@@ -484,7 +486,8 @@ int ivln_bn_train_stats_f32(const float* x, int N, int C, int HW, const float* g
 int ivln_bn_stats_from_partials_f32(const float* partials, int tiles, int C, const float* gamma, const float* beta,
                                     float* running_mean, float* running_var, float momentum, float eps, float* scale,
                                     float* shift, float* save_mean, float* save_rstd, void* stream);
-/* CBRA tail: relu(x*scale+shift) then AvgPool2d(2) (map_encoder.py:16-19). */
+/* CBRA tail: relu(x*scale+shift) then AvgPool2d(2) (map_encoder.py:16-19).  H and W even; x on an 8-byte boundary
+ * and img_stride / chan_stride / slab_stride even (two pixels per load), else IVLN_E_INVALID. */
 int ivln_scale_shift_relu_avgpool2_f32(const float* x, const float* scale, const float* shift, float* y,
                                        int N, int C, int H, int W, int64_t img_stride, int64_t chan_stride,
                                        int splits, int64_t slab_stride, void* stream);
@@ -562,14 +565,17 @@ int ivln_gru_dirs_bwd_f32(const float* dout, const float* out, const float* save
 /* The two consumers of an encoder's feature map in the MapCMA head in ONE launch (models/map_cma_policy.py:156-171,
  * 180-185, 276-296): feat (rows, C, P) contiguous ->  kv (rows, Ckv, P) = nn.Conv1d(C, Ckv, 1)  and
  * lin[r*ld_lin + o] = act(nn.Linear(C*P, O) of the flattened row).  rows <= 8 and rows*C*P*4 B <= 150 KB of LDS,
- * else IVLN_E_UNSUPPORTED (the caller runs ivln_gemm_f32 + ivln_linear_skinny_f32). */
+ * else IVLN_E_UNSUPPORTED (the caller runs ivln_gemm_f32 + ivln_linear_skinny_f32).  feat and w_lin on 16-byte
+ * boundaries, else IVLN_E_INVALID. */
 int ivln_kv_linear_f32(const float* feat, int rows, int C, int P, const float* w_kv, const float* b_kv, int Ckv, float* kv,
                        const float* w_lin, const float* b_lin, int O, int relu, float* lin, int64_t ld_lin, void* stream);
-/* nn.Linear for few rows (rollout batch): y[r][o] = act(W[o].x[r] + b[o]). */
+/* nn.Linear for few rows (rollout batch): y[r][o] = act(W[o].x[r] + b[o]).  K % 4 == 0 needs ldx % 4 == 0
+ * (IVLN_E_INVALID); x or W off a 16-byte boundary is read 4 bytes at a time (same values). */
 int ivln_linear_skinny_f32(const float* x, int64_t ldx, const float* W, const float* bias, float* y,
                            int64_t ldy, int rows, int K, int O, int relu, void* stream);
 /* One masked GRU step (habitat-lab RNNStateEncoder over nn.GRU; map_cma_policy.py:314-318,346-353).
- * x (rows,I) or gi_pre (rows,3H) = W_ih x + b_ih precomputed; h_in rows with stride ldh; mask u8. */
+ * x (rows,I) or gi_pre (rows,3H) = W_ih x + b_ih precomputed; h_in rows with stride ldh; mask u8.  H, ldh (and with x:
+ * I, ldx) multiples of 4 and h_in, w_hh (and with x: x, w_ih) on 16-byte boundaries, else IVLN_E_INVALID. */
 int ivln_gru_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, int64_t ldgi,
                       const float* h_in, int64_t ldh, const uint8_t* mask, const float* w_ih,
                       const float* w_hh, const float* b_ih, const float* b_hh, float* h_out, int64_t ldo,
@@ -621,7 +627,8 @@ int ivln_attn_small2_f32(const float* q, int64_t ldq, float scale, int rows, int
                          int64_t k0_img_stride, const float* v0, int64_t v0_img_stride, int Ck0, int Cv0, float* out0,
                          int64_t ldo0, const float* k1, int64_t k1_img_stride, const float* v1, int64_t v1_img_stride,
                          int Ck1, int Cv1, float* out1, int64_t ldo1, void* stream);
-/* prev_action_embedding(((a+1)*mask).long()) (map_cma_policy.py:297-299), written to two slices. */
+/* prev_action_embedding(((a+1)*mask).long()) (map_cma_policy.py:297-299), written to two slices.  The row index is
+ * clamped to [0, n_emb - 1]: an action below -1 reads row 0, an action >= n_emb - 1 reads the last row. */
 int ivln_prev_action_embed_f32(const int64_t* prev_actions, const uint8_t* mask, const float* table,
                                int rows, int E, int n_emb, float* out1, int64_t ld1, float* out2,
                                int64_t ld2, void* stream);

@@ -113,7 +113,8 @@ __global__ __launch_bounds__(GN_THREADS) void k_groupnorm(
     // optional second group-normalised operand added before the ReLU (the bottleneck's downsample branch:
     // y = relu(GN(conv3) + GN_ds(conv_ds)), same channel/group partition): raw slabs of the downsample conv
     const float* __restrict__ x2, const float* __restrict__ gamma2, const float* __restrict__ beta2,
-    int64_t x2_img_stride, int64_t x2_chan_stride, int splits2, int64_t slab_stride2) {
+    int64_t x2_img_stride, int64_t x2_chan_stride, int splits2, int64_t slab_stride2,
+    int vec /* the launcher's: HW % 4 == 0 and every pointer / stride keeps the float4 accesses 16-byte aligned */) {
     __shared__ __attribute__((aligned(16))) float cache[GN_CACHE];
     __shared__ float red[16];
     const int img = blockIdx.x / groups, g = blockIdx.x % groups;
@@ -121,7 +122,6 @@ __global__ __launch_bounds__(GN_THREADS) void k_groupnorm(
     const int n = cpg * HW;
     const float* xp = x + (int64_t)img * x_img_stride + (int64_t)g * cpg * x_chan_stride;
     const bool cached = n <= GN_CACHE;
-    const bool vec = (HW & 3) == 0;
     // affine parameters of this thread's first float4 are fetched now, under the data loads, instead
     // of as a dependent load after the two reductions
     float g_first = 0.f, b_first = 0.f;
@@ -677,7 +677,7 @@ constexpr int SK_ROWS = 8;
 __global__ __launch_bounds__(256) void k_linear_skinny(const float* __restrict__ x, int64_t ldx,
                                                        const float* __restrict__ W, const float* __restrict__ bias,
                                                        float* __restrict__ y, int64_t ldy, int rows, int K, int O,
-                                                       int relu) {
+                                                       int relu, int vec) {
     __shared__ float part[4][SK_ROWS];
     const int o = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(256) void k_linear_skinny(const float* __restrict__
         float acc[SK_ROWS];
 #pragma unroll
         for (int r = 0; r < SK_ROWS; ++r) acc[r] = 0.f;
-        if ((K & 3) == 0) {
+        if (vec) {  // K % 4 == 0, ldx % 4 == 0, x and W on 16-byte boundaries (the launcher's check)
             for (int k = threadIdx.x * 4; k < K; k += 1024) {
                 float4 wv = *reinterpret_cast<const float4*>(wr + k);
 #pragma unroll
@@ -1389,10 +1389,18 @@ int ivln_groupnorm2_f32(const float* x, const float* gamma, const float* beta, c
     if (x2_img_stride <= 0) x2_img_stride = (int64_t)C * HW;
     if (splits < 1) splits = 1;
     if (splits2 < 1) splits2 = 1;
+    // the float4 form needs more than HW % 4 == 0: every base pointer and every stride it multiplies has to keep the
+    // accesses on 16-byte boundaries; anything else takes the scalar form (same values, 4-byte accesses)
+    const uintptr_t ptrs = (uintptr_t)x | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)x2;
+    int64_t strides = x_img_stride | x_chan_stride | y_img_stride;
+    if (residual) strides |= r_img_stride;
+    if (splits > 1) strides |= slab_stride;
+    if (x2) strides |= x2_img_stride | x2_chan_stride | (splits2 > 1 ? slab_stride2 : 0);
+    const int vec = (HW & 3) == 0 && (ptrs & 15) == 0 && (strides & 3) == 0;
     hipLaunchKernelGGL(k_groupnorm, dim3(N * groups), dim3(GN_THREADS), 0, (hipStream_t)stream, x, gamma, beta,
                        residual, y, C, HW, groups, eps, relu, x_img_stride, x_chan_stride, splits, slab_stride,
                        y_img_stride, r_img_stride, save_mean, save_rstd, x2, gamma2, beta2, x2_img_stride,
-                       x2_chan_stride, splits2, slab_stride2);
+                       x2_chan_stride, splits2, slab_stride2, vec);
     return LAUNCH_OK();
 }
 
@@ -1446,6 +1454,8 @@ int ivln_scale_shift_relu_avgpool2_f32(const float* x, const float* scale, const
     if (chan_stride <= 0) chan_stride = (int64_t)H * W;
     if (img_stride <= 0) img_stride = (int64_t)C * H * W;
     if (splits < 1) splits = 1;
+    // 8-byte loads of two neighbouring pixels: x on an 8-byte boundary and even strides (no scalar form)
+    if (((uintptr_t)x & 7) || ((img_stride | chan_stride) & 1) || (splits > 1 && (slab_stride & 1))) return IVLN_E_INVALID;
     int64_t total = (int64_t)N * C * (H / 2) * (W / 2);
     int lpo = 1;  // lanes per output: split the slab sum until ~64K threads are in flight
     while (lpo < 16 && lpo * 2 <= splits && total * lpo < 65536) lpo *= 2;
@@ -1508,6 +1518,8 @@ int ivln_kv_linear_f32(const float* feat, int rows, int C, int P, const float* w
                        const float* w_lin, const float* b_lin, int O, int relu, float* lin, int64_t ld_lin, void* stream) {
     if (!feat || !w_kv || !kv || !w_lin || !lin || rows <= 0 || C <= 0 || P <= 0 || Ckv <= 0 || O <= 0) return IVLN_E_INVALID;
     if (rows > KVL_ROWS || ((C * P) & 3)) return IVLN_E_UNSUPPORTED;
+    // feat and w_lin are read with 16-byte loads (no scalar form)
+    if (((uintptr_t)feat | (uintptr_t)w_lin) & 15) return IVLN_E_INVALID;
     const size_t bytes = sizeof(float) * (size_t)rows * (C * P + 16);
     if (bytes > 150 * 1024) return IVLN_E_UNSUPPORTED;
     static bool raised = false;
@@ -1526,8 +1538,10 @@ int ivln_linear_skinny_f32(const float* x, int64_t ldx, const float* W, const fl
                            int rows, int K, int O, int relu, void* stream) {
     if (rows <= 0 || K <= 0 || O <= 0) return IVLN_E_INVALID;
     if ((K & 3) == 0 && (ldx & 3)) return IVLN_E_INVALID;
+    // 16-byte loads of x and W only from 16-byte boundaries; a view that starts elsewhere takes the scalar loop
+    const int vec = (K & 3) == 0 && (((uintptr_t)x | (uintptr_t)W) & 15) == 0;
     hipLaunchKernelGGL(k_linear_skinny, dim3(O), dim3(256), 0, (hipStream_t)stream, x, ldx, W, bias, y, ldy,
-                       rows, K, O, relu);
+                       rows, K, O, relu, vec);
     return LAUNCH_OK();
 }
 
@@ -1536,6 +1550,8 @@ int ivln_gru_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, i
                       const float* b_hh, float* h_out, int64_t ldo, float* h_out2, int64_t ldo2, int rows, int H,
                       float* save_r, float* save_z, float* save_n, float* save_ghn, void* stream) {
     if (rows <= 0 || (H & 3) || (x && (I & 3)) || (ldh & 3) || (x && (ldx & 3))) return IVLN_E_INVALID;
+    // every operand of the dot products is read with 16-byte loads and the kernel has no scalar form
+    if ((((uintptr_t)h_in | (uintptr_t)w_hh) & 15) || (x && (((uintptr_t)x | (uintptr_t)w_ih) & 15))) return IVLN_E_INVALID;
     if (rows <= 4)
         hipLaunchKernelGGL(k_gru_step<64>, dim3(H), dim3(256), 0, (hipStream_t)stream, x, ldx, I, gi_pre, ldgi,
                            h_in, ldh, mask, w_ih, w_hh, b_ih, b_hh, h_out, ldo, h_out2, ldo2, rows, H, save_r, save_z,

@@ -13,7 +13,6 @@ case is written to train_kernels.log in the suite's log directory (beside the up
 COVERED (bottom of the file) names the test of every entry point; tests/test_train_kernel_coverage.py (CPU) pins it to
 the header."""
 import os
-import re
 
 import pytest
 import torch
@@ -25,83 +24,7 @@ DEV = "cuda:0"
 EPS = 2.0 ** -24
 E_INVALID, E_UNSUPPORTED = -1, -5
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_log_open = False
-
-
-def _log_dir():
-    """The suite's log directory: the git-ignored `*_out/` directory the other GPU tests write their parity logs to
-    (relative to the working directory, like theirs); IVLN_TEST_LOG_DIR overrides."""
-    if os.environ.get("IVLN_TEST_LOG_DIR"):
-        return os.environ["IVLN_TEST_LOG_DIR"]
-    for line in open(os.path.join(ROOT, ".gitignore")):
-        if re.fullmatch(r"\w+_out/", line.strip()):
-            return line.strip().rstrip("/")
-    return "test_logs"
-
-
-def _log(line):
-    global _log_open
-    os.makedirs(_log_dir(), exist_ok=True)
-    with open(os.path.join(_log_dir(), "train_kernels.log"), "a" if _log_open else "w") as f:
-        f.write(line + "\n")
-    _log_open = True
-
-
-class _Bar:
-    """Collects the comparisons of one case: everything is logged before anything is asserted."""
-
-    def __init__(self, case):
-        self.case, self.bad = case, []
-
-    def check(self, name, got, ref64, ref32, factor=4.0):
-        got = got.detach().cpu().double().reshape(-1)
-        r64 = ref64.detach().double().reshape(-1)
-        r32 = ref32.detach().double().reshape(-1)
-        assert got.shape == r64.shape == r32.shape, (name, got.shape, r64.shape, r32.shape)
-        err = float((got - r64).abs().max())
-        e32 = float((r32 - r64).abs().max())
-        mx = float(r64.abs().max())
-        bar = factor * e32 + 4 * EPS * mx
-        ratio = err / e32 if e32 > 0 else (0.0 if err == 0 else float("inf"))
-        ok = err <= bar  # (False for NaN)
-        line = (f"{self.case:44s} {name:10s} hip {err:.3e}  e32 {e32:.3e}  hip/e32 {ratio:8.2f}  max|ref| {mx:.3e}  "
-                f"bar {bar:.3e}  {'ok' if ok else 'OVER'}")
-        _log(line)
-        if not ok:
-            self.bad.append(line)
-        return err, bar
-
-    def within(self, name, a, b, bar):
-        """two kernel results of the same quantity: no further apart than that quantity's bar"""
-        d = float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
-        ok = d <= bar
-        _log(f"{self.case:44s} {name:10s} apart {d:.3e}  bar {bar:.3e}  {'ok' if ok else 'OVER'}")
-        if not ok:
-            self.bad.append(f"{name}: {d:.3e} apart, bar {bar:.3e}")
-
-    def done(self):
-        assert not self.bad, "\n".join(self.bad)
-
-
-def _same_bytes(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _twice(fn):
-    """fn() -> tuple of fresh fp32 output tensors; run twice, identical bytes required (fixed reduction orders)."""
-    a, b = fn(), fn()
-    torch.cuda.synchronize()
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert _same_bytes(x, y), f"output {i} differs between two runs on the same inputs"
-    return a
-
-
-def _refused(code, fn, *args, **kw):
-    """a launcher's precondition: the wrapper raises with that return code"""
-    from ivln_ce_amd._lib import IvlnError
-
-    with pytest.raises(IvlnError, match=r"\(%d\)" % code):
-        fn(*args, **kw)
+from kernel_bar import _Bar, _log, _log_dir, _refused, _same_bytes, _twice  # noqa: E402,F401  (shared with the other per-kernel files)
 
 
 def _leaf(t, dt):
