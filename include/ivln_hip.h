@@ -573,7 +573,7 @@ int ivln_kv_linear_f32(const float* feat, int rows, int C, int P, const float* w
  * (IVLN_E_INVALID); x or W off a 16-byte boundary is read 4 bytes at a time (same values). */
 int ivln_linear_skinny_f32(const float* x, int64_t ldx, const float* W, const float* bias, float* y,
                            int64_t ldy, int rows, int K, int O, int relu, void* stream);
-/* One masked GRU step (habitat-lab RNNStateEncoder over nn.GRU; map_cma_policy.py:314-318,346-353).
+/* One masked GRU step (csrc/state_rnn.hip; habitat-lab RNNStateEncoder over nn.GRU; map_cma_policy.py:314-318,346-353).
  * x (rows,I) or gi_pre (rows,3H) = W_ih x + b_ih precomputed; h_in rows with stride ldh; mask u8.  H, ldh (and with x:
  * I, ldx) multiples of 4 and h_in, w_hh (and with x: x, w_ih) on 16-byte boundaries, else IVLN_E_INVALID. */
 int ivln_gru_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, int64_t ldgi,
@@ -589,8 +589,8 @@ int ivln_gru_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, i
  * once after allocating them (ivln_seq_sync_init, or any memset): every launch clears the step counters (bytes 0..191)
  * itself, but byte 192 is a STICKY error word that only a timed-out spin ever writes and nothing in the library
  * clears - ivln_seq_sync_status on a never-zeroed workspace reports a timeout that did not happen.  With a workspace
- * and a shape inside ivln_cma_seq_persistent_ok the whole sequence is ONE persistent launch (csrc/gru_seq.hip: W_hh
- * resident in registers over 64 workgroups of 256 threads - 32 of 512 with IVLN_SEQ_UPB=16 -, h_t exchanged through
+ * and a shape inside ivln_cma_seq_persistent_ok the whole sequence is ONE persistent launch (csrc/state_rnn.hip: W_hh
+ * resident in registers over 64 workgroups of 256 threads, h_t exchanged through
  * `out` with write-through stores and one counter per step).  The single launch is taken only when the whole grid can
  * be resident at once (occupancy query x CU count >= grid: not on a 32-CU partition or with N so large that LDS admits
  * fewer workgroups than the grid) and `out` / h0 / dgh are 16-byte aligned (they are read with 16-byte buffer loads);
@@ -722,7 +722,7 @@ int ivln_rednet_fwd(const ivln_rednet_op* table, int n_ops, const uint8_t* rgb, 
  * dkv (rows, Hq+d_out, P) / mkv (rows, Hq+m_out, P) = the dep_kv / map_kv projections (keys first).
  * Outputs: x2 (rows, x2w) = [state | text | dep' | map' | prev] (the prev slice is the caller's), h_out (rows, 2, H)
  * row stride ld_ho, feats (rows, H).  ws: ivln_cma_step_ws_floats() floats of scratch (128-byte aligned).
- * IVLN_E_UNSUPPORTED outside L <= 512, P <= 16, 64-aligned widths. */
+ * IVLN_E_UNSUPPORTED outside L <= 512, P <= 16, 64-aligned widths; IVLN_E_INVALID for a NULL h_in / h_out / x2 / feats / ws. */
 typedef struct ivln_cma_step_desc {
     int rows, L, P, H, Hq, Ct, d_out, m_out, E, x2w;
     const float* state_in;
@@ -749,7 +749,7 @@ typedef struct ivln_cma_step_desc {
 } ivln_cma_step_desc;
 int64_t ivln_cma_step_ws_floats(int rows, int L, int P, int H);
 int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream);
-/* The same head for STATE_ENCODER.rnn_type LSTM (two masked LSTM encoders, csrc/lstm_state.hip's arithmetic: gates
+/* The same head for STATE_ENCODER.rnn_type LSTM (two masked LSTM encoders, csrc/rnn_cell.h's arithmetic: gates
  * i, f, g, o; h' = h * mask, c' = c * mask; pre = (W_ih x + b_ih) + (W_hh h' + b_hh)): LSTM-1 -> text attention ->
  * depth + map attention -> compress -> LSTM-2, again five dependent launches behind one call, the three middle phases
  * being the GRU form's.  It takes the SAME descriptor, read as follows: w_ih1 (4H x (d_out+m_out+E)), w_hh1 / w_ih2 /
@@ -797,7 +797,7 @@ int ivln_attn_bwd_idx_f32(const float* dout, int64_t ld_dout, const float* attn,
                           int rows, int Ck, int Cv, int I, float* dq, int64_t ld_dq, float* dk,
                           int64_t dk_img_stride, float* dv, int64_t dv_img_stride, const int* row_index, void* stream);
 int ivln_index_sum_f32(const float* src, const int* index, int rows, int64_t M, int U, float* dst, void* stream);
-/* one BPTT step of the masked GRU: gate gradients (element part) */
+/* one BPTT step of the masked GRU: gate gradients (element part); the GRU BPTT entry points are in csrc/state_rnn.hip */
 int ivln_gru_bwd_elem_f32(const float* dout, int64_t ld_dout, const float* dh_carry, const float* r,
                           const float* z, const float* n, const float* ghn, const float* h_prev, int64_t ldh,
                           const uint8_t* mask, int rows, int H, float* dgi, float* dgh, float* dhz,
@@ -878,7 +878,7 @@ int ivln_dtw_symmetric1(const double* a, int n, const double* b, int m, int dim,
                         double* distance_out);
 
 /* ------------------------------------------------------------------------------------------
- * Masked LSTM state encoder: MODEL.STATE_ENCODER.rnn_type LSTM (csrc/lstm_state.hip).
+ * Masked LSTM state encoder: MODEL.STATE_ENCODER.rnn_type LSTM (csrc/state_rnn.hip).
  * The reference builds both recurrent state encoders of MapCMANet with rnn_type=model_config.STATE_ENCODER.rnn_type
  * (models/map_cma_policy.py:183,229) and slices rnn_states by each encoder's num_recurrent_layers (:290-351); with LSTM
  * that is habitat-lab's RNNStateEncoder over nn.LSTM(input, hidden, num_layers=1): gate order i, f, g, o; in the

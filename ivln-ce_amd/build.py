@@ -22,8 +22,7 @@ SOURCES = {
     "gn_conv.hip": [],
     "depth_net.hip": [],
     "cma_step.hip": [],
-    "gru_seq.hip": [],
-    "lstm_state.hip": [],
+    "state_rnn.hip": [],
     # (GRU instruction encoder: its register arrays are indexed by fully unrolled loops only - 0 scratch bytes)
     "instr_rnn.hip": [],
     "nn_ops.hip": [],

@@ -30,7 +30,7 @@
 //    XCD-hierarchical form 6.7 us, the fence-free form with write-through payload 4.2 us at 256 workgroups.  Four of the
 //    best of those (the phases need ~512 workgroups: 15 MB of weights, one output per workgroup) still cost more than
 //    four launch boundaries of a replayed graph (3-4 us each, tools/chain_bench.hip), so the phase launches stay.  (The
-//    replay irreproducibility was not chased once the form had lost on time; the persistent sequence GRU, csrc/gru_seq.hip,
+//    replay irreproducibility was not chased once the form had lost on time; the persistent sequence GRU, csrc/state_rnn.hip,
 //    where the exchange is small enough to win, zeroes its counters with a memset node per launch, reads the exchanged
 //    state with sc1 loads only, and is tested for reproducibility under load.)
 //
@@ -40,20 +40,22 @@
 // (A first version gave each WAVE an output and looped over rows in registers on a 128-workgroup grid: 50 us slower
 // per step than the unfused chain - per-wave serial latency, not bandwidth, is what these phases are made of.)
 //
-// STATE_ENCODER.rnn_type LSTM (ivln_cma_step_lstm_fwd, second half of the file): the same five launches with two masked
-// LSTM encoders (csrc/lstm_state.hip's arithmetic and association; gates i, f, g, o; state (rows, 4, H) = [h1 | c1 | h2 | c2]):
+// STATE_ENCODER.rnn_type LSTM (ivln_cma_step_lstm_fwd): the same five launches with two masked LSTM encoders (gates i, f,
+// g, o; state (rows, 4, H) = [h1 | c1 | h2 | c2]):
 //
 //   state, c1' = LSTM1([dep_in | map_in | prev], h1 * mask, c1 * mask)      text / dep' / map' as above
 //   feats, c2' = LSTM2(ReLU(W_c [state | text | dep' | map' | prev] + b_c), h2 * mask, c2 * mask)
 //
 // The folds, the S tables, text logits, the three attentions and compress do not depend on the cell: phases 2 and 4 are
-// the SAME kernels, phase 3 the same device function.  Phases 1 and 5 and the off-chain hidden half of the second encoder
-// (now rows x 4H) have an LSTM unit with gru_unit's work split; the GRU kernels are instantiated from the code they
-// always were.  No barrier, no spin, no counter here either.
+// the SAME kernels for both, phase 3's main part the same device function.  Phases 1 and 5 and the off-chain hidden half
+// of the second encoder are templates on the cell (csrc/rnn_cell.h: the gate dots and cell formulas of the unfused step
+// kernel, csrc/state_rnn.hip, so fused and unfused differ only through the attention folds).  No barrier, no spin, no
+// counter here either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include "../../include/ivln_hip.h"
+#include "rnn_cell.h"
 
 namespace {
 
@@ -72,102 +74,108 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+// (values a later phase reads are stored with st_pub, rnn_cell.h: between kernels the boundary's release / acquire
+// would cover it too; the cost is nil)
 
-// Values a later phase reads are stored write-through at agent scope (`global_store ... sc1`): neighbouring outputs
-// share 128-byte lines but are produced by workgroups on different XCDs, and a write-through store leaves no
-// partially-updated copy of the line behind in the producing XCD's L2 (MI355X_MICROARCH.md, inter-workgroup
-// visibility).  Between kernels the boundary's release / acquire would cover it too; the cost is nil.
-__device__ __forceinline__ void st_pub(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// LPR lanes share one batch row and split K in 16-byte pieces; 256 / LPR rows are in flight per pass.  A (row, output)
-// dot product then needs one log2(LPR)-step shuffle reduction and no LDS (the layout of k_gru_step, nn_ops.hip).
-template <int LPR>
-__device__ __forceinline__ float lpr_sum(float v) {
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// one weight row against one batch row, lane l of LPR owning every LPR-th 16-byte piece of K (reduce with lpr_sum)
 template <int LPR>
 __device__ __forceinline__ float lpr_dot(const float* __restrict__ w, const float* __restrict__ x, int K, int l) {
     float a = 0.f;
-    for (int k = l * 4; k < K; k += LPR * 4) {
-        const float4 wv = *reinterpret_cast<const float4*>(w + k);
-        const float4 xv = *reinterpret_cast<const float4*>(x + k);
-        a = fmaf(wv.x, xv.x, a);
-        a = fmaf(wv.y, xv.y, a);
-        a = fmaf(wv.z, xv.z, a);
-        a = fmaf(wv.w, xv.w, a);
-    }
+    for (int k = l * 4; k < K; k += LPR * 4)
+        a = fma4(*reinterpret_cast<const float4*>(w + k), *reinterpret_cast<const float4*>(x + k), a);
     return a;
-}
-
-// ---- one masked GRU unit j for all rows (workgroup-level) ---------------------------------------------
-// gh_pre != nullptr: hidden-side pre-activations (bias included) were computed earlier (GRU-2's phase-1 half)
-template <int LPR>
-__device__ __forceinline__ void gru_unit(const Desc& D, int j, const float* x, int64_t ldx, int I, const float* w_ih,
-                                         const float* w_hh, const float* b_ih, const float* b_hh, const float* h_in,
-                                         const float* gh_pre, float* out1, int64_t ld1, float* out2, int64_t ld2) {
-    constexpr int RPB = CT / LPR;
-    const int H = D.H;
-    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
-    for (int r0 = 0; r0 < D.rows; r0 += RPB) {
-        const int row = r0 + rr;
-        const bool ok = row < D.rows;
-        const int rc = ok ? row : 0;
-        const float mk = D.mask[rc] ? 1.f : 0.f;
-        float gi[3], gh[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            gi[g] = lpr_dot<LPR>(w_ih + ((int64_t)g * H + j) * I, x + (int64_t)rc * ldx, I, l);
-            if (!gh_pre) gh[g] = lpr_dot<LPR>(w_hh + ((int64_t)g * H + j) * H, h_in + (int64_t)rc * D.ld_h, H, l);
-        }
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            gi[g] = lpr_sum<LPR>(gi[g]);
-            if (!gh_pre) gh[g] = lpr_sum<LPR>(gh[g]);
-        }
-        if (l == 0 && ok) {
-            float a[3], b[3];
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                a[g] = gi[g] + b_ih[g * H + j];
-                b[g] = gh_pre ? gh_pre[(int64_t)row * 3 * H + g * H + j] : gh[g] * mk + b_hh[g * H + j];
-            }
-            const float hp = h_in[(int64_t)row * D.ld_h + j] * mk;
-            const float rg = sigmoidf_(a[0] + b[0]);
-            const float zg = sigmoidf_(a[1] + b[1]);
-            const float ng = tanhf(a[2] + rg * b[2]);
-            const float hn = (1.f - zg) * ng + zg * hp;
-            st_pub(out1 + (int64_t)row * ld1 + j, hn);
-            if (out2) st_pub(out2 + (int64_t)row * ld2 + j, hn);
-        }
-    }
 }
 
 // scratch regions, each starting on a 128-byte line
 __host__ __device__ __forceinline__ int64_t al32(int64_t n) { return (n + 31) & ~(int64_t)31; }
 __device__ __forceinline__ float* ws_logits(const Desc& D) { return D.ws; }
 __device__ __forceinline__ float* ws_S(const Desc& D) { return D.ws + al32((int64_t)D.rows * D.L); }
-__device__ __forceinline__ float* ws_gh2(const Desc& D) { return ws_S(D) + al32((int64_t)D.rows * D.L * 2 * D.P); }
-__device__ __forceinline__ float* ws_c2(const Desc& D) { return ws_gh2(D) + al32((int64_t)D.rows * 3 * D.H); }
+__device__ __forceinline__ float* ws_c2(const Desc& D) {   // (behind the GRU's hidden half, rows x 3H)
+    return ws_S(D) + al32((int64_t)D.rows * D.L * 2 * D.P) + al32((int64_t)D.rows * 3 * D.H);
+}
 
-// ---- GRU-1 (workgroup item = hidden unit) -----------------------------------------------------------------
-template <int LPR>
+// The hidden half of the second encoder, rows x NG*H floats: the GRU's lies inside the layout, the LSTM's (rows x 4H)
+// has a region of its own BEHIND it (the rows x 3H region in the middle stays unused there, so that the shared kernels
+// find c2 where they look for it).
+template <class Cell>
+__device__ __forceinline__ float* ws_gh2(const Desc& D) {
+    if constexpr (Cell::HAS_C) return ws_c2(D) + al32((int64_t)D.rows * D.H);
+    else return ws_S(D) + al32((int64_t)D.rows * D.L * 2 * D.P);
+}
+
+// ---- one masked recurrent unit j of encoder `enc` (0 / 1) for all rows (workgroup-level) ------------------------
+// LPR lanes share one batch row and split K in 16-byte pieces; 256 / LPR rows are in flight per pass (the layout of
+// k_rnn_step, state_rnn.hip).  The state holds per encoder one slot of H floats (GRU: h) or two (LSTM: h, c), row stride
+// ld_h in, ld_ho out.  gh_pre != nullptr: the hidden-side pre-activations W_hh h' + b_hh were computed earlier
+// (side_gh2) and h is not read.  h_t -> out1 and the encoder's h slot of h_out, c_t -> its c slot.
+template <class Cell, int LPR>
+__device__ __forceinline__ void rnn_unit(const Desc& D, int j, int enc, const float* x, int64_t ldx, int I,
+                                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                                         const float* gh_pre, float* out1, int64_t ld1) {
+    constexpr int NG = Cell::NG, RPB = CT / LPR, SLOTS = Cell::HAS_C ? 2 : 1;
+    const int H = D.H;
+    const float* h_in = D.h_in + enc * SLOTS * H;
+    float* hs_out = D.h_out + enc * SLOTS * H;
+    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
+    for (int r0 = 0; r0 < D.rows; r0 += RPB) {
+        const int row = r0 + rr;
+        const bool ok = row < D.rows;
+        const int rc = ok ? row : 0;
+        const float mk = D.mask[rc] ? 1.f : 0.f;
+        float ai[NG], ah[NG];   // the reduced dots; ah = W_hh[g*H + j] . (h * mask)
+        if constexpr (Cell::HAS_C) {
+            gate_dots<NG, LPR, true>(w_ih, j, H, I, x + (int64_t)rc * ldx, 1.f, l, ai);
+            if (!gh_pre) gate_dots<NG, LPR, true>(w_hh, j, H, H, h_in + (int64_t)rc * D.ld_h, mk, l, ah);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ai[g] = lpr_sum<LPR>(ai[g]);
+                if (!gh_pre) ah[g] = lpr_sum<LPR>(ah[g]);
+            }
+        } else {
+            // The GRU unit keeps the loop it always had - K walked once per GATE, the mask applied to the finished dot -
+            // because in phase 1 the single pass holds three rows' pieces at once: 50-54 VGPRs against 40-44 and one
+            // occupancy step ("State encoders: what is shared").  mask in {0, 1}: the same values.
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ai[g] = lpr_dot<LPR>(w_ih + ((int64_t)g * H + j) * I, x + (int64_t)rc * ldx, I, l);
+                if (!gh_pre) ah[g] = lpr_dot<LPR>(w_hh + ((int64_t)g * H + j) * H, h_in + (int64_t)rc * D.ld_h, H, l);
+            }
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ai[g] = lpr_sum<LPR>(ai[g]);
+                if (!gh_pre) ah[g] = lpr_sum<LPR>(ah[g]) * mk;
+            }
+        }
+        if (l == 0 && ok) {
+            float gi[NG], gh[NG], sv[5];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                gi[g] = ai[g] + b_ih[g * H + j];
+                gh[g] = gh_pre ? gh_pre[(int64_t)row * NG * H + g * H + j] : ah[g] + b_hh[g * H + j];
+            }
+            // the state element the formula carries: h (GRU) or c (LSTM, the slot behind h)
+            const float prev = h_in[(Cell::HAS_C ? H : 0) + (int64_t)row * D.ld_h + j] * mk;
+            const float hn = Cell::fwd(gi, gh, prev, sv);
+            st_pub(out1 + (int64_t)row * ld1 + j, hn);
+            st_pub(hs_out + (int64_t)row * D.ld_ho + j, hn);
+            if constexpr (Cell::HAS_C) st_pub(hs_out + H + (int64_t)row * D.ld_ho + j, sv[4]);
+        }
+    }
+}
+
+// ---- encoder 1 (workgroup item = hidden unit) ---------------------------------------------------------------
+template <class Cell, int LPR>
 __device__ void phase1(const Desc& D, int wg, int nwg) {
     const int sin_w = D.d_out + D.m_out + D.E;
     for (int j = wg; j < D.H; j += nwg)
-        gru_unit<LPR>(D, j, D.state_in, sin_w, sin_w, D.w_ih1, D.w_hh1, D.b_ih1, D.b_hh1, D.h_in, nullptr, D.x2, D.x2w,
-                      D.h_out, D.ld_ho);
+        rnn_unit<Cell, LPR>(D, j, 0, D.state_in, sin_w, sin_w, D.w_ih1, D.w_hh1, D.b_ih1, D.b_hh1, nullptr, D.x2, D.x2w);
 }
 
-// ---- hidden half of GRU-2: gh2[r][g*H + j] = W_hh2[g*H + j] . (h2[r] * mask[r]) + b_hh2 (item = unit j).  Depends on
+// ---- hidden half of encoder 2: gh2[r][g*H + j] = W_hh2[g*H + j] . (h2[r] * mask[r]) + b_hh2 (item = unit j).  Depends on
 // nothing but the incoming state, so it rides in the attention phase's launch, off the chain. ----
-template <int LPR>
+template <class Cell, int LPR>
 __device__ void side_gh2(const Desc& D, int wg, int nwg) {
-    constexpr int RPB = CT / LPR;
+    constexpr int NG = Cell::NG, RPB = CT / LPR, SLOTS = Cell::HAS_C ? 2 : 1;
     const int H = D.H;
     const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
     for (int j = wg; j < H; j += nwg) {
@@ -176,11 +184,12 @@ __device__ void side_gh2(const Desc& D, int wg, int nwg) {
             const bool ok = row < D.rows;
             const int rc = ok ? row : 0;
             const float mk = D.mask[rc] ? 1.f : 0.f;
+            float ah[NG];
+            gate_dots<NG, LPR, true>(D.w_hh2, j, H, H, D.h_in + SLOTS * H + (int64_t)rc * D.ld_h, mk, l, ah);
 #pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                float v = lpr_dot<LPR>(D.w_hh2 + ((int64_t)g * H + j) * H, D.h_in + H + (int64_t)rc * D.ld_h, H, l);
-                v = lpr_sum<LPR>(v);
-                if (l == 0 && ok) st_pub(ws_gh2(D) + (int64_t)row * 3 * H + g * H + j, v * mk + D.b_hh2[g * H + j]);
+            for (int g = 0; g < NG; ++g) {
+                const float v = lpr_sum<LPR>(ah[g]);
+                if (l == 0 && ok) st_pub(ws_gh2<Cell>(D) + (int64_t)row * NG * H + g * H + j, v + D.b_hh2[g * H + j]);
             }
         }
     }
@@ -358,179 +367,65 @@ __device__ void phase4(const Desc& D, int wg, int nwg) {
     }
 }
 
-// ---- phase 5: GRU-2 (input half here, hidden half from phase 1) ----------------------------------------
-template <int LPR>
+// ---- phase 5: encoder 2 (input half here, hidden half from side_gh2) ------------------------------------------
+template <class Cell, int LPR>
 __device__ void phase5(const Desc& D, int wg, int nwg) {
     for (int j = wg; j < D.H; j += nwg)
-        gru_unit<LPR>(D, j, ws_c2(D), D.H, D.H, D.w_ih2, D.w_hh2, D.b_ih2, D.b_hh2, D.h_in + D.H, ws_gh2(D), D.feats, D.H,
-                      D.h_out + D.H, D.ld_ho);
+        rnn_unit<Cell, LPR>(D, j, 1, ws_c2(D), D.H, D.H, D.w_ih2, D.w_hh2, D.b_ih2, D.b_hh2, ws_gh2<Cell>(D), D.feats, D.H);
 }
 
 // One kernel per phase.  Work that is off the chain shares a launch with the phase it can hide behind: the first
-// `main` workgroups run the phase, the rest the side work.
-template <int PH, int LPR>
+// `main` workgroups run the phase, the rest the side work.  Phases 2 and 4 hold no cell arithmetic (Cell = void).
+template <int PH, int LPR, class Cell = void>
 __global__ __launch_bounds__(CT) void k_cma_phase(const Desc D, int main) {
     const int wg = blockIdx.x, nwg = gridDim.x;
-    if constexpr (PH == 1) phase1<LPR>(D, wg, nwg);
+    if constexpr (PH == 1) phase1<Cell, LPR>(D, wg, nwg);
     if constexpr (PH == 2) {
         if (wg < main) phase2(D, wg, main);
         else side_S(D, wg - main, nwg - main);
     }
     if constexpr (PH == 3) {
         if (wg < main) phase3(D, wg, main);
-        else side_gh2<LPR>(D, wg - main, nwg - main);
+        else side_gh2<Cell, LPR>(D, wg - main, nwg - main);
     }
     if constexpr (PH == 4) phase4<LPR>(D, wg, nwg);
-    if constexpr (PH == 5) phase5<LPR>(D, wg, nwg);
+    if constexpr (PH == 5) phase5<Cell, LPR>(D, wg, nwg);
 }
 
-template <int LPR>
-void launch_cma(const Desc& D, int mode, hipStream_t s) {
+template <int LPR, class Cell>
+void launch_cma(const Desc& D, hipStream_t s) {
     const int tiles = (D.L + 15) / 16;
     const int chunks = (D.Ct + D.d_out + D.m_out) / 16;
-    (void)mode;
-    hipLaunchKernelGGL((k_cma_phase<1, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+    hipLaunchKernelGGL((k_cma_phase<1, LPR, Cell>), dim3(D.H), dim3(CT), 0, s, D, D.H);
     hipLaunchKernelGGL((k_cma_phase<2, LPR>), dim3(D.rows * tiles + D.rows * D.L), dim3(CT), 0, s, D, D.rows * tiles);
-    hipLaunchKernelGGL((k_cma_phase<3, LPR>), dim3(D.rows * chunks + D.H), dim3(CT), 0, s, D, D.rows * chunks);
+    hipLaunchKernelGGL((k_cma_phase<3, LPR, Cell>), dim3(D.rows * chunks + D.H), dim3(CT), 0, s, D, D.rows * chunks);
     hipLaunchKernelGGL((k_cma_phase<4, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
-    hipLaunchKernelGGL((k_cma_phase<5, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+    hipLaunchKernelGGL((k_cma_phase<5, LPR, Cell>), dim3(D.H), dim3(CT), 0, s, D, D.H);
 }
 
-// ======== LSTM state encoders (STATE_ENCODER.rnn_type LSTM) ===============================================
-// The same five phases with LSTM arithmetic in the two encoders.  Phases 2 and 4 ARE the kernels above and phase 3's
-// main part is `phase3`: text logits, the three attentions and compress do not know the cell type, and they address the
-// scratch by the layout above.  What differs: four gate rows per unit (torch's order i, f, g, o), a cell state beside
-// the hidden state - the state is (rows, 4, H) = [h1 | c1 | h2 | c2] - and a hidden half of rows x 4H floats, which has a
-// region of its own BEHIND the layout above (the rows x 3H region in the middle stays unused here, so that the shared
-// kernels find c2 where they look for it).
-__device__ __forceinline__ float* ws_gh2_lstm(const Desc& D) { return ws_c2(D) + al32((int64_t)D.rows * D.H); }
-
-__device__ __forceinline__ float fma4(const float4 w, const float4 v, float a) {
-    a = fmaf(w.x, v.x, a);
-    a = fmaf(w.y, v.y, a);
-    a = fmaf(w.z, v.z, a);
-    return fmaf(w.w, v.w, a);
+// what both entry points ask of a descriptor
+int check_desc(const Desc* d) {
+    // (h_in / h_out: every unit reads and writes the state; a NULL h_out used to reach phase 5 as the address H * 4)
+    if (!d || d->rows <= 0 || !d->ws || !d->x2 || !d->feats || !d->h_in || !d->h_out) return IVLN_E_INVALID;
+    if (d->L <= 0 || d->L > MAX_L || d->P <= 0 || d->P > 16) return IVLN_E_UNSUPPORTED;
+    if ((d->H & 63) || (d->Hq & 15) || (d->Ct & 15) || (d->d_out & 15) || (d->m_out & 15)) return IVLN_E_UNSUPPORTED;
+    const int sin_w = d->d_out + d->m_out + d->E;
+    if ((sin_w & 3) || (d->x2w & 3) || (d->ld_h & 3) || d->x2w != d->H + d->Ct + d->d_out + d->m_out + d->E)
+        return IVLN_E_UNSUPPORTED;
+    return IVLN_OK;
 }
 
-// the four gate rows of unit j against one row of x (scaled by mk: the mask of the incoming state, 1 for an input):
-// one pass over K, each 16-byte piece of x loaded once for the four rows (the loop of k_lstm_step, lstm_state.hip)
-template <int LPR>
-__device__ __forceinline__ void lstm_dot4(const float* __restrict__ w, int j, int H, int K, const float* __restrict__ x,
-                                          float mk, int l, float (&a)[4]) {
-    for (int k = l * 4; k < K; k += LPR * 4) {
-        float4 xv = *reinterpret_cast<const float4*>(x + k);
-        xv.x *= mk, xv.y *= mk, xv.z *= mk, xv.w *= mk;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) a[g] = fma4(*reinterpret_cast<const float4*>(w + ((int64_t)g * H + j) * K + k), xv, a[g]);
-    }
-}
-
-// ---- one masked LSTM unit j for all rows (the work split of gru_unit) ---------------------------------
-// h_in / c_in: the encoder's two slots of the incoming state (row stride ld_h); gh_pre != nullptr: the hidden-side
-// pre-activations W_hh h' + b_hh were computed earlier (side_gh2_lstm) and h_in is not read.  h_t -> out1 and hs_out,
-// c_t -> cs_out (the encoder's two slots of the outgoing state, row stride ld_ho).  Association as in k_lstm_step:
-// pre = (W_ih x + b_ih) + (W_hh h' + b_hh), the mask applied to h and c BEFORE they are used.
-template <int LPR>
-__device__ __forceinline__ void lstm_unit(const Desc& D, int j, const float* x, int64_t ldx, int I, const float* w_ih,
-                                          const float* w_hh, const float* b_ih, const float* b_hh, const float* h_in,
-                                          const float* c_in, const float* gh_pre, float* out1, int64_t ld1, float* hs_out,
-                                          float* cs_out) {
-    constexpr int RPB = CT / LPR;
-    const int H = D.H;
-    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
-    for (int r0 = 0; r0 < D.rows; r0 += RPB) {
-        const int row = r0 + rr;
-        const bool ok = row < D.rows;
-        const int rc = ok ? row : 0;
-        const float mk = D.mask[rc] ? 1.f : 0.f;
-        float ai[4] = {0.f, 0.f, 0.f, 0.f}, ah[4] = {0.f, 0.f, 0.f, 0.f};
-        lstm_dot4<LPR>(w_ih, j, H, I, x + (int64_t)rc * ldx, 1.f, l, ai);
-        if (!gh_pre) lstm_dot4<LPR>(w_hh, j, H, H, h_in + (int64_t)rc * D.ld_h, mk, l, ah);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            ai[g] = lpr_sum<LPR>(ai[g]);
-            if (!gh_pre) ah[g] = lpr_sum<LPR>(ah[g]);
-        }
-        if (l == 0 && ok) {
-            float pre[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float gi = ai[g] + b_ih[g * H + j];
-                pre[g] = gi + (gh_pre ? gh_pre[(int64_t)row * 4 * H + g * H + j] : ah[g] + b_hh[g * H + j]);
-            }
-            const float cp = c_in[(int64_t)row * D.ld_h + j] * mk;
-            const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf(pre[2]), og = sigmoidf_(pre[3]);
-            const float ct = fg * cp + ig * gg;
-            const float ht = og * tanhf(ct);
-            st_pub(out1 + (int64_t)row * ld1 + j, ht);
-            st_pub(hs_out + (int64_t)row * D.ld_ho + j, ht);
-            st_pub(cs_out + (int64_t)row * D.ld_ho + j, ct);
-        }
-    }
-}
-
-// ---- LSTM-1: state slots 0 (h1) and 1 (c1) -------------------------------------------------------------
-template <int LPR>
-__device__ void phase1_lstm(const Desc& D, int wg, int nwg) {
-    const int sin_w = D.d_out + D.m_out + D.E;
-    for (int j = wg; j < D.H; j += nwg)
-        lstm_unit<LPR>(D, j, D.state_in, sin_w, sin_w, D.w_ih1, D.w_hh1, D.b_ih1, D.b_hh1, D.h_in, D.h_in + D.H, nullptr,
-                       D.x2, D.x2w, D.h_out, D.h_out + D.H);
-}
-
-// ---- hidden half of LSTM-2: gh2[r][g*H + j] = W_hh2[g*H + j] . (h2[r] * mask[r]) + b_hh2, h2 = state slot 2; rides in
-// the attention phase's launch as side_gh2 does ----
-template <int LPR>
-__device__ void side_gh2_lstm(const Desc& D, int wg, int nwg) {
-    constexpr int RPB = CT / LPR;
-    const int H = D.H;
-    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
-    for (int j = wg; j < H; j += nwg) {
-        for (int r0 = 0; r0 < D.rows; r0 += RPB) {
-            const int row = r0 + rr;
-            const bool ok = row < D.rows;
-            const int rc = ok ? row : 0;
-            const float mk = D.mask[rc] ? 1.f : 0.f;
-            float ah[4] = {0.f, 0.f, 0.f, 0.f};
-            lstm_dot4<LPR>(D.w_hh2, j, H, H, D.h_in + 2 * H + (int64_t)rc * D.ld_h, mk, l, ah);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float v = lpr_sum<LPR>(ah[g]);
-                if (l == 0 && ok) st_pub(ws_gh2_lstm(D) + (int64_t)row * 4 * H + g * H + j, v + D.b_hh2[g * H + j]);
-            }
-        }
-    }
-}
-
-// ---- LSTM-2: input half here, hidden half from side_gh2_lstm; state slots 2 (h2) and 3 (c2) ------------
-template <int LPR>
-__device__ void phase5_lstm(const Desc& D, int wg, int nwg) {
-    for (int j = wg; j < D.H; j += nwg)
-        lstm_unit<LPR>(D, j, ws_c2(D), D.H, D.H, D.w_ih2, D.w_hh2, D.b_ih2, D.b_hh2, D.h_in + 2 * D.H, D.h_in + 3 * D.H,
-                       ws_gh2_lstm(D), D.feats, D.H, D.h_out + 2 * D.H, D.h_out + 3 * D.H);
-}
-
-// the three launches that hold cell arithmetic; phases 2 and 4 are k_cma_phase<2> / <4>
-template <int PH, int LPR>
-__global__ __launch_bounds__(CT) void k_cma_lstm_phase(const Desc D, int main) {
-    const int wg = blockIdx.x, nwg = gridDim.x;
-    if constexpr (PH == 1) phase1_lstm<LPR>(D, wg, nwg);
-    if constexpr (PH == 3) {
-        if (wg < main) phase3(D, wg, main);
-        else side_gh2_lstm<LPR>(D, wg - main, nwg - main);
-    }
-    if constexpr (PH == 5) phase5_lstm<LPR>(D, wg, nwg);
-}
-
-template <int LPR>
-void launch_cma_lstm(const Desc& D, hipStream_t s) {
-    const int tiles = (D.L + 15) / 16;
-    const int chunks = (D.Ct + D.d_out + D.m_out) / 16;
-    hipLaunchKernelGGL((k_cma_lstm_phase<1, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
-    hipLaunchKernelGGL((k_cma_phase<2, LPR>), dim3(D.rows * tiles + D.rows * D.L), dim3(CT), 0, s, D, D.rows * tiles);
-    hipLaunchKernelGGL((k_cma_lstm_phase<3, LPR>), dim3(D.rows * chunks + D.H), dim3(CT), 0, s, D, D.rows * chunks);
-    hipLaunchKernelGGL((k_cma_phase<4, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
-    hipLaunchKernelGGL((k_cma_lstm_phase<5, LPR>), dim3(D.H), dim3(CT), 0, s, D, D.H);
+// 64 / 32 / 16 lanes per row: 4 / 8 / 16 rows in flight per pass
+template <class Cell>
+int run_cma(const Desc* d, void* stream) {
+    Desc D = *d;
+    if (D.Mq_img <= 0) D.Mq_img = (int64_t)(D.H + 1) * D.L;
+    if (D.TQb_img <= 0) D.TQb_img = (int64_t)D.Hq * D.L;
+    hipStream_t s = (hipStream_t)stream;
+    if (D.rows <= 4) launch_cma<64, Cell>(D, s);
+    else if (D.rows <= 8) launch_cma<32, Cell>(D, s);
+    else launch_cma<16, Cell>(D, s);
+    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
 }
 
 }  // namespace
@@ -543,20 +438,9 @@ int64_t ivln_cma_step_ws_floats(int rows, int L, int P, int H) {
 }
 
 int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
-    if (!d || d->rows <= 0 || !d->ws || !d->x2 || !d->feats) return IVLN_E_INVALID;
-    if (d->L <= 0 || d->L > MAX_L || d->P <= 0 || d->P > 16) return IVLN_E_UNSUPPORTED;
-    if ((d->H & 63) || (d->Hq & 15) || (d->Ct & 15) || (d->d_out & 15) || (d->m_out & 15)) return IVLN_E_UNSUPPORTED;
-    const int sin_w = d->d_out + d->m_out + d->E;
-    if ((sin_w & 3) || (d->x2w & 3) || (d->ld_h & 3) || d->x2w != d->H + d->Ct + d->d_out + d->m_out + d->E)
-        return IVLN_E_UNSUPPORTED;
-    Desc D = *d;
-    if (D.Mq_img <= 0) D.Mq_img = (int64_t)(D.H + 1) * D.L;
-    if (D.TQb_img <= 0) D.TQb_img = (int64_t)D.Hq * D.L;
-    hipStream_t s = (hipStream_t)stream;
-    if (D.rows <= 4) launch_cma<64>(D, mode, s);
-    else if (D.rows <= 8) launch_cma<32>(D, mode, s);
-    else launch_cma<16>(D, mode, s);
-    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+    (void)mode;
+    const int rc = check_desc(d);
+    return rc != IVLN_OK ? rc : run_cma<GruCell>(d, stream);
 }
 
 int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H) {
@@ -566,27 +450,16 @@ int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H) {
 
 int ivln_cma_step_lstm_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
     (void)mode;
-    if (!d || d->rows <= 0 || !d->ws || !d->x2 || !d->feats || !d->h_in || !d->h_out) return IVLN_E_INVALID;
-    if (d->L <= 0 || d->L > MAX_L || d->P <= 0 || d->P > 16) return IVLN_E_UNSUPPORTED;
-    if (d->H <= 0 || (d->H & 63) || (d->Hq & 15) || (d->Ct & 15) || (d->d_out & 15) || (d->m_out & 15)) return IVLN_E_UNSUPPORTED;
-    const int sin_w = d->d_out + d->m_out + d->E;
-    if ((sin_w & 3) || (d->x2w & 3) || (d->ld_h & 3) || (d->ld_ho & 3) ||
-        d->x2w != d->H + d->Ct + d->d_out + d->m_out + d->E)
-        return IVLN_E_UNSUPPORTED;
+    const int rc = check_desc(d);
+    if (rc != IVLN_OK) return rc;
+    if (d->H <= 0 || (d->ld_ho & 3)) return IVLN_E_UNSUPPORTED;
     // every workgroup reads whole rows of h_in while others write h_out: the (rows, 4, H) views must not share memory
     const int64_t G = (int64_t)4 * d->H;
     if (d->ld_h < G || d->ld_ho < G) return IVLN_E_INVALID;
     const float *in0 = d->h_in, *in1 = d->h_in + (int64_t)(d->rows - 1) * d->ld_h + G;
     const float *out0 = d->h_out, *out1 = d->h_out + (int64_t)(d->rows - 1) * d->ld_ho + G;
     if ((uintptr_t)in0 < (uintptr_t)out1 && (uintptr_t)out0 < (uintptr_t)in1) return IVLN_E_INVALID;
-    Desc D = *d;
-    if (D.Mq_img <= 0) D.Mq_img = (int64_t)(D.H + 1) * D.L;
-    if (D.TQb_img <= 0) D.TQb_img = (int64_t)D.Hq * D.L;
-    hipStream_t s = (hipStream_t)stream;
-    if (D.rows <= 4) launch_cma_lstm<64>(D, s);
-    else if (D.rows <= 8) launch_cma_lstm<32>(D, s);
-    else launch_cma_lstm<16>(D, s);
-    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+    return run_cma<LstmCell>(d, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Non-GEMM forward kernels of the MapCMA hot path for gfx950 (all fp32, NCHW):
 // GroupNorm(+residual,+ReLU), BatchNorm statistics / folding, pooling, one-hot map features,
-// embedding + lengths, bidirectional LSTM recurrence, masked GRU step, skinny (B<=8 rows)
+// embedding + lengths, bidirectional LSTM recurrence, skinny (B<=8 rows)
 // linear, cross-modal attention, arg-max heads.  Each entry point cites the reference op it
 // replaces.  These are HBM/L2-bound or latency-bound element/reduction kernels: 64-wide wave
 // reductions via DPP shuffles, LDS for per-block staging, coalesced NCHW row accesses.
@@ -8,7 +8,6 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/ivln_hip.h"
-#include "gru_seq.h"
 
 namespace {
 
@@ -43,7 +42,6 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     for (int i = 0; i < nw; ++i) s = fmaxf(s, red[i]);
     return s;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------
 // GroupNorm (+ residual) (+ ReLU): one 512-thread block per (image, group), float4 accesses.
@@ -802,96 +800,6 @@ __global__ __launch_bounds__(256) void k_kv_linear(const float* __restrict__ fea
 }
 
 // ------------------------------------------------------------------------------------------
-// Masked GRU step (habitat-lab RNNStateEncoder single_forward / one step of seq_forward wrapping
-// nn.GRU; call sites models/map_cma_policy.py:314-318,346-353).  One block per hidden unit j; the six
-// weight rows W_ih[{r,z,n}][j], W_hh[{r,z,n}][j] are dotted with 8 (or 4) rows at a time:
-//   gi = W_ih x + b_ih  (or precomputed gi when x == nullptr);  gh = W_hh (h*mask) + b_hh
-//   r = s(gi_r+gh_r)  z = s(gi_z+gh_z)  n = tanh(gi_n + r*gh_n)  h' = (1-z)*n + z*h
-// Optional saves for BPTT: (rows, H) each of r, z, n, gh_n.
-// ------------------------------------------------------------------------------------------
-template <int LPR>
-__global__ __launch_bounds__(256) void k_gru_step(const float* __restrict__ x, int64_t ldx, int I,
-                                                  const float* __restrict__ gi_pre, int64_t ldgi,
-                                                  const float* __restrict__ h_in, int64_t ldh,
-                                                  const uint8_t* __restrict__ mask,
-                                                  const float* __restrict__ w_ih, const float* __restrict__ w_hh,
-                                                  const float* __restrict__ b_ih, const float* __restrict__ b_hh,
-                                                  float* __restrict__ h_out, int64_t ldo,
-                                                  float* __restrict__ h_out2, int64_t ldo2, int rows, int H,
-                                                  float* __restrict__ save_r, float* __restrict__ save_z,
-                                                  float* __restrict__ save_n, float* __restrict__ save_ghn) {
-    // LPR lanes share one row: each lane owns every LPR-th float4 of K, so a (row, unit) needs one
-    // log2(LPR)-step shuffle reduction of 6 values and no LDS / barrier (the previous wave-splits-K form
-    // spent most of its 13 us in 48 full-wave reductions per block)
-    constexpr int RPB = 256 / LPR;  // rows per pass
-    const int j = blockIdx.x;
-    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
-    for (int r0 = 0; r0 < rows; r0 += RPB) {
-        const int row = r0 + rr;
-        const bool row_ok = row < rows;
-        const int rowc = row_ok ? row : 0;
-        float ai[3] = {0.f, 0.f, 0.f}, ah[3] = {0.f, 0.f, 0.f};
-        if (x) {
-            const float* xr = x + (int64_t)rowc * ldx;
-            for (int k = l * 4; k < I; k += LPR * 4) {
-                const float4 xv = *reinterpret_cast<const float4*>(xr + k);
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const float4 wv = *reinterpret_cast<const float4*>(w_ih + ((int64_t)g * H + j) * I + k);
-                    ai[g] = fmaf(wv.x, xv.x, ai[g]);
-                    ai[g] = fmaf(wv.y, xv.y, ai[g]);
-                    ai[g] = fmaf(wv.z, xv.z, ai[g]);
-                    ai[g] = fmaf(wv.w, xv.w, ai[g]);
-                }
-            }
-        }
-        const float mk = mask ? (mask[rowc] ? 1.f : 0.f) : 1.f;
-        const float* hr = h_in + (int64_t)rowc * ldh;
-        for (int k = l * 4; k < H; k += LPR * 4) {
-            float4 hv = *reinterpret_cast<const float4*>(hr + k);
-            hv.x *= mk, hv.y *= mk, hv.z *= mk, hv.w *= mk;
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                const float4 wv = *reinterpret_cast<const float4*>(w_hh + ((int64_t)g * H + j) * H + k);
-                ah[g] = fmaf(wv.x, hv.x, ah[g]);
-                ah[g] = fmaf(wv.y, hv.y, ah[g]);
-                ah[g] = fmaf(wv.z, hv.z, ah[g]);
-                ah[g] = fmaf(wv.w, hv.w, ah[g]);
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off > 0; off >>= 1) {
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                if (x) ai[g] += __shfl_xor(ai[g], off, 64);
-                ah[g] += __shfl_xor(ah[g], off, 64);
-            }
-        }
-        if (l == 0 && row_ok) {
-            float gi[3], gh[3];
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                gi[g] = x ? ai[g] + b_ih[g * H + j] : gi_pre[(int64_t)row * ldgi + g * H + j];
-                gh[g] = ah[g] + b_hh[g * H + j];
-            }
-            float hp = h_in[(int64_t)row * ldh + j] * mk;
-            float rg = sigmoidf_(gi[0] + gh[0]);
-            float zg = sigmoidf_(gi[1] + gh[1]);
-            float ng = tanhf(gi[2] + rg * gh[2]);
-            float hn = (1.f - zg) * ng + zg * hp;
-            h_out[(int64_t)row * ldo + j] = hn;
-            if (h_out2) h_out2[(int64_t)row * ldo2 + j] = hn;
-            if (save_r) {
-                save_r[(int64_t)row * H + j] = rg;
-                save_z[(int64_t)row * H + j] = zg;
-                save_n[(int64_t)row * H + j] = ng;
-                save_ghn[(int64_t)row * H + j] = gh[2];
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // Cross-modal attention (MapCMANet._attn, models/map_cma_policy.py:266-274): per row n
 //   logits[i] = sum_c q[n][c] k[n][c][i];  masked i: logits - 1e8;  attn = softmax(logits*scale)
 //   out[n][c'] = sum_i attn[i] v[n][c'][i]
@@ -1542,60 +1450,6 @@ int ivln_linear_skinny_f32(const float* x, int64_t ldx, const float* W, const fl
     const int vec = (K & 3) == 0 && (((uintptr_t)x | (uintptr_t)W) & 15) == 0;
     hipLaunchKernelGGL(k_linear_skinny, dim3(O), dim3(256), 0, (hipStream_t)stream, x, ldx, W, bias, y, ldy,
                        rows, K, O, relu, vec);
-    return LAUNCH_OK();
-}
-
-int ivln_gru_step_f32(const float* x, int64_t ldx, int I, const float* gi_pre, int64_t ldgi, const float* h_in,
-                      int64_t ldh, const uint8_t* mask, const float* w_ih, const float* w_hh, const float* b_ih,
-                      const float* b_hh, float* h_out, int64_t ldo, float* h_out2, int64_t ldo2, int rows, int H,
-                      float* save_r, float* save_z, float* save_n, float* save_ghn, void* stream) {
-    if (rows <= 0 || (H & 3) || (x && (I & 3)) || (ldh & 3) || (x && (ldx & 3))) return IVLN_E_INVALID;
-    // every operand of the dot products is read with 16-byte loads and the kernel has no scalar form
-    if ((((uintptr_t)h_in | (uintptr_t)w_hh) & 15) || (x && (((uintptr_t)x | (uintptr_t)w_ih) & 15))) return IVLN_E_INVALID;
-    if (rows <= 4)
-        hipLaunchKernelGGL(k_gru_step<64>, dim3(H), dim3(256), 0, (hipStream_t)stream, x, ldx, I, gi_pre, ldgi,
-                           h_in, ldh, mask, w_ih, w_hh, b_ih, b_hh, h_out, ldo, h_out2, ldo2, rows, H, save_r, save_z,
-                           save_n, save_ghn);
-    else
-        hipLaunchKernelGGL(k_gru_step<32>, dim3(H), dim3(256), 0, (hipStream_t)stream, x, ldx, I, gi_pre, ldgi,
-                           h_in, ldh, mask, w_ih, w_hh, b_ih, b_hh, h_out, ldo, h_out2, ldo2, rows, H, save_r, save_z,
-                           save_n, save_ghn);
-    return LAUNCH_OK();
-}
-
-/* GRU over a whole time-major sequence batch in ONE call: T dependent k_gru_step launches enqueued from C.  The
- * per-timestep Python -> ctypes round trip (~15 us) was longer than the 6.5 us kernel, so the 128 forward steps of
- * an update left the GPU idle for ~1 ms (profiles/r02_update_kernel_stats.csv); enqueued back to back they are
- * GPU-bound.  gi = W_ih x + b_ih for all T*N rows (one GEMM, done by the caller). */
-int ivln_cma_seq_fwd_f32(const float* gi, const float* h0, int64_t ld_h0, const uint8_t* masks, const float* w_hh,
-                         const float* b_hh, float* out, int64_t ldo, float* state_out, int64_t ld_so, int T, int N,
-                         int H, float* save_r, float* save_z, float* save_n, float* save_ghn, void* sync_ws,
-                         void* stream) {
-    if (!gi || !h0 || !masks || !w_hh || !b_hh || !out || T <= 0 || N <= 0 || (H & 3) || (ld_h0 & 3) || (ldo & 3))
-        return IVLN_E_INVALID;
-    if (sync_ws && T > 1 && ivln_cma_seq_persistent_ok(N, H, 0)) {   // one persistent launch (gru_seq.hip)
-        const int rc = ivln_gru_seq_fwd_persistent(gi, h0, ld_h0, masks, w_hh, b_hh, out, ldo, state_out, ld_so, T, N,
-                                                   save_r, save_z, save_n, save_ghn, sync_ws, stream);
-        if (rc != IVLN_E_UNSUPPORTED) return rc;
-    }
-    for (int t = 0; t < T; ++t) {
-        const int64_t r0 = (int64_t)t * N;
-        const float* h_in = t == 0 ? h0 : out + (r0 - N) * ldo;
-        const int64_t ldh = t == 0 ? ld_h0 : ldo;
-        float* so = (t == T - 1) ? state_out : nullptr;
-        float* sr = save_r ? save_r + r0 * H : nullptr;
-        float* sz = save_r ? save_z + r0 * H : nullptr;
-        float* sn = save_r ? save_n + r0 * H : nullptr;
-        float* sg = save_r ? save_ghn + r0 * H : nullptr;
-        if (N <= 4)
-            hipLaunchKernelGGL(k_gru_step<64>, dim3(H), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, (int64_t)0,
-                               0, gi + r0 * 3 * H, (int64_t)3 * H, h_in, ldh, masks + r0, (const float*)nullptr, w_hh,
-                               (const float*)nullptr, b_hh, out + r0 * ldo, ldo, so, ld_so, N, H, sr, sz, sn, sg);
-        else
-            hipLaunchKernelGGL(k_gru_step<32>, dim3(H), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, (int64_t)0,
-                               0, gi + r0 * 3 * H, (int64_t)3 * H, h_in, ldh, masks + r0, (const float*)nullptr, w_hh,
-                               (const float*)nullptr, b_hh, out + r0 * ldo, ldo, so, ld_so, N, H, sr, sz, sn, sg);
-    }
     return LAUNCH_OK();
 }
 

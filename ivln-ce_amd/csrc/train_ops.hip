@@ -9,7 +9,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/ivln_hip.h"
-#include "gru_seq.h"
+#include "rnn_cell.h"
 
 namespace {
 
@@ -278,44 +278,6 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const float* __restrict__ dout
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// GRU BPTT, element part of one step (rows = N sequences of step t):
-//   dh = dout + dh_carry;  dn = dh(1-z); dz = dh(hp - n); dhz = dh z
-//   dn_pre = dn(1-n^2); dz_pre = dz z(1-z); dr_pre = dn_pre ghn r(1-r)
-//   dgi = [dr_pre, dz_pre, dn_pre];  dgh = [dr_pre, dz_pre, dn_pre r];  hp = h_prev*mask
-// The matvec dh_prev = dgh . W_hh then runs through k_linear_skinny_ex with (+dhz)*mask epilogue.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gru_bwd_elem(const float* __restrict__ dout, int64_t ld_dout,
-                                                      const float* __restrict__ dh_carry,
-                                                      const float* __restrict__ r, const float* __restrict__ z,
-                                                      const float* __restrict__ n, const float* __restrict__ ghn,
-                                                      const float* __restrict__ h_prev, int64_t ldh,
-                                                      const uint8_t* __restrict__ mask, int rows, int H,
-                                                      float* __restrict__ dgi, float* __restrict__ dgh,
-                                                      float* __restrict__ dhz, float* __restrict__ hp_out) {
-    int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * H) return;
-    int row = idx / H, j = idx % H;
-    float dh = dout[(int64_t)row * ld_dout + j] + (dh_carry ? dh_carry[idx] : 0.f);
-    float mk = mask[row] ? 1.f : 0.f;
-    float hp = h_prev[(int64_t)row * ldh + j] * mk;
-    float rg = r[idx], zg = z[idx], ng = n[idx], gh = ghn[idx];
-    float dn = dh * (1.f - zg);
-    float dz = dh * (hp - ng);
-    float dn_pre = dn * (1.f - ng * ng);
-    float dz_pre = dz * zg * (1.f - zg);
-    float dr_pre = dn_pre * gh * rg * (1.f - rg);
-    int64_t o = (int64_t)row * 3 * H + j;
-    dgi[o] = dr_pre;
-    dgi[o + H] = dz_pre;
-    dgi[o + 2 * H] = dn_pre;
-    dgh[o] = dr_pre;
-    dgh[o + H] = dz_pre;
-    dgh[o + 2 * H] = dn_pre * rg;
-    dhz[idx] = dh * zg;
-    hp_out[idx] = hp;
-}
-
 // y[r][o] = (W[o].x[r] + add[r][o]) * (rowmask[r] ? 1 : 0)   (skinny rows; see k_linear_skinny)
 // One block per output o, 32 lanes per row (8 rows per pass): each lane owns every 32nd float4 of K and a
 // (row, o) costs one 5-step shuffle reduction - no LDS, no barrier.
@@ -332,82 +294,11 @@ __global__ __launch_bounds__(256) void k_linear_skinny_ex(const float* __restric
         const int row = r0 + rr;
         const bool row_ok = row < rows;
         const float* xr = x + (int64_t)(row_ok ? row : 0) * ldx;
-        float a0 = 0.f, a1 = 0.f;
-        for (int k = l * 4; k < K; k += 128) {
-            const float4 wv = *reinterpret_cast<const float4*>(wr + k);
-            const float4 xv = *reinterpret_cast<const float4*>(xr + k);
-            a0 = fmaf(wv.x, xv.x, a0);
-            a1 = fmaf(wv.y, xv.y, a1);
-            a0 = fmaf(wv.z, xv.z, a0);
-            a1 = fmaf(wv.w, xv.w, a1);
-        }
-        float v = a0 + a1;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        float v = skinny_dot32(wr, xr, K, l);
         if (l == 0 && row_ok) {
             if (add) v += add[(int64_t)row * ld_add + o];
             if (rowmask) v = rowmask[row] ? v : 0.f;
             y[(int64_t)row * ldy + o] = v;
-        }
-    }
-}
-
-// One BPTT step of the masked GRU in ONE launch: block j first finishes step t for hidden unit j,
-//   dh_prev[row][j] = (W_hh^T[j] . dgh_t[row] + dhz[row][j]) * mask_t[row]        (k_linear_skinny_ex)
-// and, since the element part of step t-1 for unit j needs nothing but that value, runs it right away
-// (k_gru_bwd_elem on column j).  Halves the launches of the BPTT chain (2 x 126 per GRU per update).
-__global__ __launch_bounds__(256) void k_gru_bwd_step(
-    const float* __restrict__ dgh_t, int64_t ld_dgh, const float* __restrict__ Wt, const uint8_t* __restrict__ mask_t,
-    const float* __restrict__ dout_p, int64_t ld_dout, const float* __restrict__ r, const float* __restrict__ z,
-    const float* __restrict__ n, const float* __restrict__ ghn, const float* __restrict__ h_pp, int64_t ldh,
-    const uint8_t* __restrict__ mask_p, int rows, int H, float* __restrict__ dhz, float* __restrict__ dgi_p,
-    float* __restrict__ dgh_p, float* __restrict__ hp_p) {
-    const int j = blockIdx.x;
-    const int l = threadIdx.x & 31, rr = threadIdx.x >> 5;
-    const int K = 3 * H;
-    const float* wr = Wt + (int64_t)j * K;
-    for (int r0 = 0; r0 < rows; r0 += 8) {
-        const int row = r0 + rr;
-        const bool row_ok = row < rows;
-        const int rowc = row_ok ? row : 0;
-        const float* xr = dgh_t + (int64_t)rowc * ld_dgh;
-        // the element part's inputs do not depend on the matvec: fetch them first, under its loads
-        const int idx = rowc * H + j;
-        const float e_dout = dout_p[(int64_t)rowc * ld_dout + j], e_dhz = dhz[idx];
-        const float e_h = h_pp[(int64_t)rowc * ldh + j];
-        const float rg = r[idx], zg = z[idx], ng = n[idx], gh = ghn[idx];
-        const bool e_mt = mask_t[rowc] != 0, e_mp = mask_p[rowc] != 0;
-        float a0 = 0.f, a1 = 0.f;
-        for (int k = l * 4; k < K; k += 128) {
-            const float4 wv = *reinterpret_cast<const float4*>(wr + k);
-            const float4 xv = *reinterpret_cast<const float4*>(xr + k);
-            a0 = fmaf(wv.x, xv.x, a0);
-            a1 = fmaf(wv.y, xv.y, a1);
-            a0 = fmaf(wv.z, xv.z, a0);
-            a1 = fmaf(wv.w, xv.w, a1);
-        }
-        float v = a0 + a1;
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (l == 0 && row_ok) {
-            v = e_mt ? v + e_dhz : 0.f;  // dh carried into step t-1
-            // ---- element part of step t-1 (k_gru_bwd_elem) ----
-            const float dh = e_dout + v;
-            const float hp = e_mp ? e_h : 0.f;
-            const float dn = dh * (1.f - zg);
-            const float dz = dh * (hp - ng);
-            const float dn_pre = dn * (1.f - ng * ng);
-            const float dz_pre = dz * zg * (1.f - zg);
-            const float dr_pre = dn_pre * gh * rg * (1.f - rg);
-            const int64_t o = (int64_t)row * 3 * H + j;
-            dgi_p[o] = dr_pre;
-            dgi_p[o + H] = dz_pre;
-            dgi_p[o + 2 * H] = dn_pre;
-            dgh_p[o] = dr_pre;
-            dgh_p[o + H] = dz_pre;
-            dgh_p[o + 2 * H] = dn_pre * rg;
-            dhz[idx] = dh * zg;
-            hp_p[idx] = hp;
         }
     }
 }
@@ -962,63 +853,6 @@ int ivln_attn_bwd_f32(const float* dout, int64_t ld_dout, const float* attn, con
                       float* dv, int64_t dv_img_stride, void* stream) {
     return ivln_attn_bwd_idx_f32(dout, ld_dout, attn, q, ldq, k, k_img_stride, v, v_img_stride, scale, rows, Ck, Cv, I, dq, ld_dq,
                                  dk, dk_img_stride, dv, dv_img_stride, nullptr, stream);
-}
-
-int ivln_gru_bwd_elem_f32(const float* dout, int64_t ld_dout, const float* dh_carry, const float* r, const float* z,
-                          const float* n, const float* ghn, const float* h_prev, int64_t ldh, const uint8_t* mask,
-                          int rows, int H, float* dgi, float* dgh, float* dhz, float* hp_out, void* stream) {
-    hipLaunchKernelGGL(k_gru_bwd_elem, dim3(nblk((int64_t)rows * H)), dim3(256), 0, (hipStream_t)stream, dout, ld_dout,
-                       dh_carry, r, z, n, ghn, h_prev, ldh, mask, rows, H, dgi, dgh, dhz, hp_out);
-    return LAUNCH_OK();
-}
-
-int ivln_gru_bwd_step_f32(const float* dgh_t, int64_t ld_dgh, const float* whh_t, const uint8_t* mask_t,
-                          const float* dout_prev, int64_t ld_dout, const float* r, const float* z, const float* n,
-                          const float* ghn, const float* h_prev, int64_t ldh, const uint8_t* mask_prev, int rows, int H,
-                          float* dhz, float* dgi_prev, float* dgh_prev, float* hp_prev, void* stream) {
-    if ((H & 3) || (ld_dgh & 3) || rows <= 0) return IVLN_E_INVALID;
-    hipLaunchKernelGGL(k_gru_bwd_step, dim3(H), dim3(256), 0, (hipStream_t)stream, dgh_t, ld_dgh, whh_t, mask_t,
-                       dout_prev, ld_dout, r, z, n, ghn, h_prev, ldh, mask_prev, rows, H, dhz, dgi_prev, dgh_prev,
-                       hp_prev);
-    return LAUNCH_OK();
-}
-
-/* BPTT of ivln_cma_seq_fwd_f32 in one call: the element part of step T-1, then T-1 fused (carry of step t + element
- * part of step t-1) launches, enqueued from C (see the forward).  whh_t = W_hh^T (H, 3H).  Outputs dgi / dgh
- * (T*N, 3H), hp = h_prev * mask (T*N, H); dhz (N, H) is scratch. */
-int ivln_cma_seq_bwd_f32(const float* d_out, int64_t ld_dout, const float* r, const float* z, const float* n,
-                         const float* ghn, const float* out, int64_t ld_out, const float* h0, int64_t ld_h0,
-                         const uint8_t* masks, const float* whh_t, int T, int N, int H, float* dgi, float* dgh, float* hp,
-                         float* dhz, void* sync_ws, void* stream) {
-    if (!d_out || !r || !out || !h0 || !masks || !whh_t || !dgi || !dgh || !hp || !dhz || T <= 0 || N <= 0 || (H & 3))
-        return IVLN_E_INVALID;
-    if (sync_ws && T > 1 && ivln_cma_seq_persistent_ok(N, H, 1)) {   // one persistent launch (gru_seq.hip)
-        const int rc = ivln_gru_seq_bwd_persistent(d_out, ld_dout, r, z, n, ghn, out, ld_out, h0, ld_h0, masks, whh_t, T, N,
-                                                   dgi, dgh, hp, sync_ws, stream);
-        if (rc != IVLN_E_UNSUPPORTED) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    auto hprev = [&](int t, int64_t& ld) -> const float* {  // hidden state entering step t
-        ld = t == 0 ? ld_h0 : ld_out;
-        return t == 0 ? h0 : out + (int64_t)(t - 1) * N * ld_out;
-    };
-    {
-        const int64_t r0 = (int64_t)(T - 1) * N;
-        int64_t ld;
-        const float* hpv = hprev(T - 1, ld);
-        hipLaunchKernelGGL(k_gru_bwd_elem, dim3(nblk((int64_t)N * H)), dim3(256), 0, s, d_out + r0 * ld_dout, ld_dout,
-                           (const float*)nullptr, r + r0 * H, z + r0 * H, n + r0 * H, ghn + r0 * H, hpv, ld, masks + r0, N,
-                           H, dgi + r0 * 3 * H, dgh + r0 * 3 * H, dhz, hp + r0 * H);
-    }
-    for (int t = T - 1; t > 0; --t) {
-        const int64_t rt = (int64_t)t * N, rp = (int64_t)(t - 1) * N;
-        int64_t ld;
-        const float* hpp = hprev(t - 1, ld);
-        hipLaunchKernelGGL(k_gru_bwd_step, dim3(H), dim3(256), 0, s, dgh + rt * 3 * H, (int64_t)3 * H, whh_t, masks + rt,
-                           d_out + rp * ld_dout, ld_dout, r + rp * H, z + rp * H, n + rp * H, ghn + rp * H, hpp, ld,
-                           masks + rp, N, H, dhz, dgi + rp * 3 * H, dgh + rp * 3 * H, hp + rp * H);
-    }
-    return LAUNCH_OK();
 }
 
 int ivln_linear_skinny_ex_f32(const float* x, int64_t ldx, const float* W, const float* add, int64_t ld_add,

@@ -141,6 +141,15 @@ def _L():
         L.ivln_add_f32.argtypes = [vp, vp, vp, i64, i32, vp]
         L.ivln_copy2d_f32.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp]
         L.ivln_tour_memory_f32.argtypes = [vp, i64, vp, i64, vp, i32, i32, vp, i64, vp, i64, vp]
+        # recurrent state encoders (csrc/state_rnn.hip)
+        L.ivln_seq_sync_init.argtypes = L.ivln_seq_sync_status.argtypes = [vp, vp]
+        L.ivln_cma_seq_fwd_f32.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.ivln_lstm_step_f32.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp,
+                                         i64, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.ivln_lstm_seq_fwd_f32.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp,
+                                            vp, vp, vp, vp, vp]
+        L.ivln_lstm_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32,
+                                            vp, vp, vp, i64, vp, i64, vp]
         _sigs_done = True
     return L
 
@@ -1381,7 +1390,7 @@ _seq_sync_ws = {}
 
 
 def _seq_ws(device):
-    """256-byte counter / error workspace of the single-launch sequence GRU (csrc/gru_seq.hip), one per stream: two
+    """256-byte counter / error workspace of the single-launch sequence GRU (csrc/state_rnn.hip), one per stream: two
     sequences in flight on different streams must not share a counter.  None -> the per-timestep launches."""
     if not SEQ_PERSISTENT:
         return None
@@ -1412,7 +1421,6 @@ def seq_recover():
     import logging
 
     L = _L()
-    L.ivln_seq_sync_init.argtypes = [vp, vp]
     for ws in _seq_sync_ws.values():
         check(L.ivln_seq_sync_init(dptr(ws), stream_ptr()), "ivln_seq_sync_init")
     torch.cuda.synchronize()
@@ -1426,7 +1434,6 @@ def check_seq_sync():
     """Raise if a bounded spin of a persistent sequence launch timed out (synchronises the stream: call where the
     host waits anyway, e.g. after reading the loss).  A timed-out launch ends on its own; its outputs are garbage."""
     L = _L()
-    L.ivln_seq_sync_status.argtypes = [vp, vp]
     for ws in _seq_sync_ws.values():
         check(L.ivln_seq_sync_status(dptr(ws), stream_ptr()), "ivln_seq_sync_status (persistent GRU spin timed out)")
 
@@ -1459,7 +1466,6 @@ def gru_seq(gi, h0, masks_u8, w_hh, b_hh, out, state_out, T, N, saves=None):
     H = w_hh.shape[1]
     sv = saves or (None, None, None, None)
     L = _L()
-    L.ivln_cma_seq_fwd_f32.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     check(L.ivln_cma_seq_fwd_f32(dptr(gi), _p(h0), h0.stride(0), dptr(masks_u8), dptr(w_hh), dptr(b_hh), _p(out),
                                  out.stride(0), _p(state_out), state_out.stride(0) if state_out is not None else 0, T, N,
                                  H, _p(sv[0]), _p(sv[1]), _p(sv[2]), _p(sv[3]), _p(_seq_ws(gi.device)), stream_ptr()),
@@ -1469,8 +1475,6 @@ def gru_seq(gi, h0, masks_u8, w_hh, b_hh, out, state_out, T, N, saves=None):
 def gru_seq_bwd(d_out, r, z, n, ghn, out, h0, masks_u8, whh_t, T, N, dgi, dgh, hp, dhz):
     H = r.shape[1]
     L = _T()
-    L.ivln_cma_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp,
-                                       vp, vp]
     check(L.ivln_cma_seq_bwd_f32(_p(d_out), d_out.stride(0), dptr(r), dptr(z), dptr(n), dptr(ghn), _p(out), out.stride(0),
                                  _p(h0), h0.stride(0), dptr(masks_u8), dptr(whh_t), T, N, H, dptr(dgi), dptr(dgh), dptr(hp),
                                  dptr(dhz), _p(_seq_ws(r.device)), stream_ptr()), "ivln_cma_seq_bwd_f32")
@@ -1487,8 +1491,6 @@ def lstm_step(x, gi_pre, h_in, c_in, mask_u8, w_ih, w_hh, b_ih, b_hh, h_out, c_o
     H = w_hh.shape[1]
     s = saves or (None,) * 5
     L = _L()
-    L.ivln_lstm_step_f32.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64,
-                                     i32, i32, vp, vp, vp, vp, vp, vp]
     check(
         L.ivln_lstm_step_f32(_p(x), _ld(x), w_ih.shape[1] if x is not None else 0, _p(gi_pre), _ld(gi_pre), _p(h_in),
                              h_in.stride(0), _p(c_in), c_in.stride(0), _p(mask_u8), dptr(w_ih) if x is not None else None,
@@ -1505,8 +1507,6 @@ def lstm_seq(gi, h0, c0, masks_u8, w_hh, b_hh, out, h_state_out, c_state_out, T,
     H = w_hh.shape[1]
     s = saves or (None,) * 5
     L = _L()
-    L.ivln_lstm_seq_fwd_f32.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, vp,
-                                        vp, vp, vp, vp]
     check(L.ivln_lstm_seq_fwd_f32(dptr(gi), _p(h0), h0.stride(0), _p(c0), c0.stride(0), dptr(masks_u8), dptr(w_hh),
                                   dptr(b_hh), _p(out), out.stride(0), _p(h_state_out), _ld(h_state_out), _p(c_state_out),
                                   c_state_out.stride(0), T, N, H, *[_p(t) for t in s], stream_ptr()),
@@ -1518,8 +1518,6 @@ def lstm_seq_bwd(d_out, saves, out, h0, c0, masks_u8, whh_t, T, N, dgi, hp, dh0,
     W_hh^T (H,4H) -> dgi (T*N,4H), hp (T*N,H) = masked h_{t-1}, dh0 / dc0 (N,H) row-strided."""
     H = whh_t.shape[0]
     L = _L()
-    L.ivln_lstm_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, vp,
-                                        vp, vp, i64, vp, i64, vp]
     check(L.ivln_lstm_seq_bwd_f32(_p(d_out), d_out.stride(0), *[dptr(t) for t in saves], _p(out), out.stride(0), _p(h0),
                                   h0.stride(0), _p(c0), c0.stride(0), dptr(masks_u8), dptr(whh_t), T, N, H, dptr(dgi),
                                   dptr(hp), _p(dh0), dh0.stride(0), _p(dc0), dc0.stride(0), stream_ptr()),
@@ -1707,7 +1705,7 @@ def copy2d(src, dst, rows, cols, broadcast_rows=False):
     )
 
 
-# ---- backward / loss / optimizer bindings (csrc/train_ops.hip, csrc/instr_rnn.hip) ----------------
+# ---- backward / loss / optimizer bindings (csrc/train_ops.hip, csrc/state_rnn.hip, csrc/instr_rnn.hip) ----------------
 _tsigs_done = False
 
 
@@ -1724,6 +1722,10 @@ def _T():
         L.ivln_attn_bwd_f32.argtypes = [vp, i64, vp, vp, i64, vp, i64, vp, i64, f32, i32, i32, i32, i32, vp, i64, vp,
                                         i64, vp, i64, vp]
         L.ivln_gru_bwd_elem_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp]
+        L.ivln_gru_bwd_step_f32.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp,
+                                            vp]
+        L.ivln_cma_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp,
+                                           vp, vp]
         L.ivln_linear_skinny_ex_f32.argtypes = [vp, i64, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]
         L.ivln_lstm_dirs_bwd_f32.argtypes = [vp] * 7 + [i32, i32, i32, i32, vp, vp, vp, vp, vp]
         L.ivln_gru_dirs_bwd_f32.argtypes = [vp] * 6 + [i32, i32, i32, i32] + [vp] * 7
@@ -1889,8 +1891,6 @@ def gru_bwd_step(dgh_t, whh_t, mask_t, dout_prev, r, z, n, ghn, h_prev, mask_pre
     """Fused BPTT step: carry of step t (matvec + dhz, masked) -> element part of step t-1."""
     rows, H = r.shape
     L = _T()
-    L.ivln_gru_bwd_step_f32.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp,
-                                        vp]
     check(
         L.ivln_gru_bwd_step_f32(_p(dgh_t), dgh_t.stride(0), dptr(whh_t), _p(mask_t), _p(dout_prev), dout_prev.stride(0),
                                 _p(r), _p(z), _p(n), _p(ghn), _p(h_prev), h_prev.stride(0), _p(mask_prev), rows, H,

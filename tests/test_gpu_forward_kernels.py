@@ -880,7 +880,7 @@ def _gru_ref(x, gi_pre, h_in, mask, w_ih, w_hh, b_ih, b_hh, dt):
 @pytest.mark.parametrize("rows", [4, 5, 9, 33])
 @pytest.mark.parametrize("H,I", [(8, 4), (64, 36)])
 def test_gru_step(H, I, rows):
-    """k_gru_step: 64 lanes per row up to 4 rows, 32 from 5 (8 rows per pass: 9 and 33 need a second / fifth pass with one live
+    """k_rnn_step<GruCell>: 64 lanes per row up to 4 rows, 32 from 5 (8 rows per pass: 9 and 33 need a second / fifth pass with one live
     row).  H = 8, I = 4: two / one lanes of a row carry data; H = 64, I = 36: I is no multiple of the 32-lane stride.  Mask
     given or NULL, the x path and the gi_pre path; h_in, h_out and h_out2 are column slices; the four saves go against
     float64."""

@@ -1517,7 +1517,7 @@ def _gru_seq_run(ops, case, T, N, persistent, backward):
 
 @pytest.mark.parametrize("T,N", [(64, 8), (7, 5), (33, 16), (5, 3), (12, 40), (2, 1)])
 def test_persistent_sequence_gru_matches_per_step_launches_and_torch(T, N):
-    """ivln_cma_seq_fwd/bwd as ONE persistent launch each (csrc/gru_seq.hip) against the launch-per-timestep path of
+    """ivln_cma_seq_fwd/bwd as ONE persistent launch each (csrc/state_rnn.hip) against the launch-per-timestep path of
     the same entry points (sync_ws = NULL): same summation order, 1e-6 (measured 2e-7: the compiler contracts the
     element formulas differently in the two kernels); the
     forward also against torch's own GRU arithmetic (masked nn.GRUCell recurrence, 1e-5).  N > 16 exercises the

@@ -1,5 +1,5 @@
 """GPU: `MODEL.STATE_ENCODER.rnn_type: LSTM` - the masked LSTM step, its sequence form and its BPTT
-(csrc/lstm_state.hip) alone against float64, then the MapCMA policy built with it: rollout steps, one update, and
+(csrc/state_rnn.hip) alone against float64, then the MapCMA policy built with it: rollout steps, one update, and
 hipGraph replay.
 
 The reference of the kernel tests is `torch.nn.LSTM` in float64 driven step by step with h and c multiplied by the
@@ -252,7 +252,7 @@ def _seq_forward(ops, c, w, saves=True):
     return dict(gi=gi, h0=h0, c0=c0, out=out, wide=wide, state=state, saves=sv, masks=masks)
 
 
-SEQ_SHAPES = [(1, 2, 64), (5, 3, 128), (4, 8, 512)]
+SEQ_SHAPES = [(1, 2, 64), (5, 3, 128), (4, 8, 512), (3, 9, 64)]   # (N = 9: a second pass of the step kernel, one live row)
 
 
 @pytest.mark.parametrize("T,N,H", SEQ_SHAPES)

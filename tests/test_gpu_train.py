@@ -151,7 +151,7 @@ def test_hip_update_agent_matches_reference_loss_and_moves_params():
 
 
 def test_update_whose_persistent_gru_timed_out_is_skipped_on_the_device_and_run_again():
-    """VERDICT r4 item 7 for the update: the sequence GRUs run as ONE persistent launch each (csrc/gru_seq.hip) whose
+    """VERDICT r4 item 7 for the update: the sequence GRUs run as ONE persistent launch each (csrc/state_rnn.hip) whose
     workgroups exchange through bounded spins.  When a workgroup never arrives (word 49 of the sync workspace: workgroup 1
     leaves at entry, what a workgroup the dispatcher could not place looks like) the launch times out and the update's
     gradients are void.  The Adam kernel then skips the step ON THE DEVICE (its guard word = the sticky error), the host
