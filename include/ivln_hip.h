@@ -208,7 +208,8 @@ typedef struct ivln_gemm_desc {
      * below 2^-23 of a product, i.e. the result is as close to the exact convolution as the fp32 MFMA kernel's
      * (csrc/conv_bf3.hip).  tile_override 9 insists on this kernel (IVLN_E_UNSUPPORTED when not eligible), 20 + c on its tile
      * configuration c = 0 ... 6 (tuning: tools/conv_cfg_sweep.py);
-     * IVLN_NO_SPLIT_BF16 in the environment keeps the fp32 MFMA kernels (A/B).  A must still be given. */
+     * no environment switch turns it off on the C side: a caller that wants the fp32 MFMA kernels leaves A_split null.
+     * A must still be given. */
     const void* A_split;
     int64_t a_split_grp_stride;
     /* 1: the weight gradient of a 7x7 same-size conv (A_NCHW_P x B_IM2COL_T -> dense) may run on the same split-bf16

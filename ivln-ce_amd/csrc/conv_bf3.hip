@@ -1,16 +1,6 @@
 // Direct stride-1 3x3 / 7x7 convolution with fp32 operands carried as THREE bf16 pieces each, on the bf16 MFMA pipe
-// (gfx950: v_mfma_f32_32x32x16_bf16 issues 16x the FLOPs of v_mfma_f32_32x32x2_f32 per cycle).
-//
-//   x = x1 + x2 + x3: x1 = bf16(x) (round to nearest even), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2); the remainders are
-//   exact in fp32, |x2| <= 2^-8 |x|, |x3| <= 2^-16 |x|, and what the three pieces miss is below 2^-25 |x| - an fp32
-//   significand is 24 bits, bf16 has fp32's exponent range (below 2^-110 the last piece runs out of exponent; infinities
-//   and NaNs travel in x1 alone: a non-finite input never gives a finite output, but an infinity can come out as NaN).
-//   a * b = (a1 + a2 + a3)(b1 + b2 + b3): of the nine piece products the kernel issues the six of relative size >= 2^-16 -
-//   a1b1, a1b2, a2b1, a1b3, a2b2, a3b1 - each exact in the MFMA (8 x 8 significand bits) and accumulated in fp32 like
-//   the fp32 MFMA accumulates its products; the three it drops (a2b3, a3b2 <= 2^-24 |a b| each, a3b3) sum to less than
-//   2^-23 |a b| - the size of fp32's own rounding of the product.  Measured against float64 the result is as close as the
-//   fp32 MFMA kernel's (tests/test_gpu_kernels.py: both within the same bar, error tables in DESIGN.md section 3).
-//   Six bf16 MFMAs of K = 16 replace eight fp32 MFMAs of K = 2: 192 instead of 512 pipe cycles per 16 channels x 1 tap.
+// (gfx950: v_mfma_f32_32x32x16_bf16 issues 16x the FLOPs of v_mfma_f32_32x32x2_f32 per cycle).  The arithmetic and the pieces
+// every kernel here shares - product ladder, record store, quad epilogue, partial tiles through LDS - are in bf3_common.h.
 //
 // Users: the map CNN's four 7x7 convs and their input gradients (map_encoder.py:8-97 under base_il_trainer.py:173-219),
 // RedNet's 3x3 convs (rednet.py:190-358).  Data flow per workgroup (512 threads = 8 waves, 2 per SIMD):
@@ -27,93 +17,14 @@
 
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "bf3_common.h"
 #include "residency.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-
-constexpr int PIXB = 112;   // bytes per staged pixel: 3 pieces x 16 channels x 2 bytes + 16 of padding
-constexpr int CB = 16;      // input channels per chunk = K of one MFMA
-
-__host__ __device__ constexpr int bf3_taps_padded(int KS) { return KS == 7 ? 54 : (KS == 3 ? 9 : (KS == 2 ? 4 : 1)); }  // multiple of every prefetch depth used (3, 6 | 3, 9 | 2, 4)
-// KS == 2: the 2 x 2 window of the stacked output-parity classes of a stride-2 3x3 transposed conv (IVLN_B_CONV_K2 ->
-// IVLN_D_NCHW_UP2X4, rednet.py:152-181: taps at input offsets 0..1, pad 0, the row / column past the edge reads as zero; rows
-// m = 4 * channel + class, a row's pixel (ho, wo) is output pixel (2 ho + a, 2 wo + b) of channel m / 4).
-// Patch geometry of a (PTH x PTW) tile: rows ho0 - pad .. + PTH + KS - 2; columns on a grid of aligned 16-byte groups that
-// starts bf3_gx0(KS) pixels left of the tile (odd kernels need the left halo's group, the 2 x 2 window does not).
-__host__ __device__ constexpr int bf3_gx0(int KS) { return KS == 2 ? 0 : 4; }
-__host__ __device__ constexpr int bf3_xoff(int KS) { return KS == 2 ? 0 : 4 - KS / 2; }  // patch column x = pixel x + XOFF of the group grid
-__host__ __device__ constexpr int bf3_stage_chunks(int KS) { return KS == 1 ? 4 : 1; }  // 16-channel chunks staged per barrier pair (1x1: one tap per chunk)
-
-// x -> the upper 16 bits of its three pieces (see the header): round-to-nearest-even at each step, remainders exact.
-__device__ __forceinline__ uint32_t bf16_rne_bits(float v, bool& fin) {
-    const uint32_t u = __float_as_uint(v);
-    fin = (u & 0x7F800000u) != 0x7F800000u;
-    uint32_t hb = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
-    if (fin && (hb & 0x7F800000u) == 0x7F800000u) hb = u & 0xFFFF0000u;  // (next to FLT_MAX: do not round a finite value to infinity)
-    if (!fin) hb = (u & 0xFFFF0000u) | ((u & 0x007FFFFFu) ? 0x00400000u : 0u);  // infinity as it is; a NaN stays a NaN
-    return hb;
-}
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    bool fin, f2;
-    const uint32_t hb = bf16_rne_bits(x, fin);
-    const float r = fin ? __fsub_rn(x, __uint_as_float(hb)) : 0.f;  // (infinities and NaNs travel in the first piece alone)
-    const uint32_t mb = bf16_rne_bits(r, f2);
-    const float r2 = __fsub_rn(r, __uint_as_float(mb));
-    const uint32_t lb = bf16_rne_bits(r2, f2);
-    h = hb >> 16;
-    m = mb >> 16;
-    l = lb >> 16;
-}
-
-// Two values at once, on v_cvt_pk_bf16_f32 (round to nearest even, two floats -> one packed word: first value in the low half):
-// 11 VALU operations per pair and piece set instead of ~40.  What the staging passes use; non-finite values: the first piece
-// carries them, the remainders turn NaN (the header's "an infinity can come out as NaN"), and a finite value within 2^-9 of
-// FLT_MAX rounds its first piece to infinity.
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void split3_pair(float v0, float v1, uint32_t& H, uint32_t& M, uint32_t& L) {
-    H = cvt_pk_bf16(v0, v1);
-    const float r0 = __fsub_rn(v0, __uint_as_float(H << 16)), r1 = __fsub_rn(v1, __uint_as_float(H & 0xFFFF0000u));
-    M = cvt_pk_bf16(r0, r1);
-    const float q0 = __fsub_rn(r0, __uint_as_float(M << 16)), q1 = __fsub_rn(r1, __uint_as_float(M & 0xFFFF0000u));
-    L = cvt_pk_bf16(q0, q1);
-}
-
-#ifdef BF3_TIMING  // tools/conv_bf3_phases.py: per-workgroup phase sums (100 MHz wall clock): prologue, staging, MFMA, epilogue
+#ifdef BF3_TIMING  // tools/conv_bf3_phases.py: per-workgroup phase sums (BF3_T of bf3_common.h)
 __device__ unsigned long long g_bf3_stamp[8192 * 8];  // records of 8 words
-#define BF3_T() (threadIdx.x == 0 ? wall_clock64() : 0ull)
-#else
-#define BF3_T() 0ull
 #endif
-
-// Behind a 16-byte buffer store issued straight from computed registers: four wait states, pinned in place, before anything
-// may write the store's data registers again.  The store unit reads its data a few cycles after issue, 16 lanes at a time;
-// the compiler pads for that only in the cases its hazard table lists, and on this part a VALU write right behind such a
-// store (scalar channel offset in soffset) was seen to land first in lanes 48-63 - one register of one store stale, once in
-// a few thousand workgroups, run-to-run different (tools/dbg_fuse.py: the fused bottleneck tail against the two launches).
-#ifdef BF3_NO_STORE_GUARD  // (tools/check_store_hazard.py's self-test: the checker has to find these sites unguarded)
-#define BF3_STORE_GUARD() do {} while (0)
-#else
-#define BF3_STORE_GUARD()                       \
-    do {                                        \
-        __builtin_amdgcn_sched_barrier(0);      \
-        asm volatile("s_nop 3" ::: "memory");   \
-        __builtin_amdgcn_sched_barrier(0);      \
-    } while (0)
-#endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bf3_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 
 // ST = 2 (round 6): the stride-2 3x3 convs of RedNet's layer 2-4 entry blocks (rednet.py:84-110, pad 1, Hin = 2 Hout).  Output
 // (ho, wo) reads input rows 2 ho - 1 .. 2 ho + 1: the patch is staged as FOUR PHASE PLANES - (row parity, column parity) of the
@@ -156,70 +67,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
     const int grp = p.grp_imgs > 0 ? img0 / p.grp_imgs : 0;
 
     // Staging work of a thread.
-    // 3x3 / 7x7 (round 5): an ITEM = one aligned 16-byte group of four pixels of a patch row x one channel pair - two
-    // buffer_load_b128 (one per channel) through an SGPR descriptor with the chunk's channel base in the scalar offset.  W is
-    // a multiple of 4 and the groups start at multiples of 4 pixels of the image row, so a group lies wholly inside the
-    // row or wholly outside: what is outside (halo past the image, images past the batch, channels past Cin) gets an
-    // out-of-range offset and the hardware returns zeros - no selects, no per-element validity.  Item -> lane: the pair
-    // index fastest, then the group (the LDS writes of 32 lanes then hit 16 banks twice: free; a wave's loads touch whole
-    // 128-byte lines).  Six loads per thread and chunk where the first version issued 32 four-byte loads with ~10 address
-    // operations each, and - the loads being unconditional - the compiler knows how many are in flight at every tap: the
-    // first version's `if (c + 1 < c_end) load_patch` made it wait for the NEXT chunk's patch (an HBM round trip) at the
-    // first tap of every chunk (s_waitcnt vmcnt(13) with 50 loads in flight).
+    // 3x3 / 7x7 / 2x2: its items of the aligned-group scheme (Bf3GroupStager; stride 2: into the four phase planes).  The loads
+    // being unconditional, the compiler knows how many are in flight at every tap: the first version's
+    // `if (c + 1 < c_end) load_patch` made it wait for the NEXT chunk's patch (an HBM round trip) at the first tap of every
+    // chunk (s_waitcnt vmcnt(13) with 50 loads in flight).
     // 1x1 (CS chunks per stage, no halo): the flat (pixel, pair) enumeration with offsets re-derived per stage.
-    constexpr int XOFF = bf3_xoff(KS);               // patch column x is pixel x + XOFF of the aligned group grid
-    // stride 2: input rows 2 ho0 - 1 .. 2 ho0 + 2 PTH - 1 (2 PTH + 1 of them), columns on the group grid that starts at 2 wo0 - 4
-    constexpr int PROWS = S2 ? 2 * PTH + 1 : PH;     // INPUT rows staged per image
-    constexpr int NG = S2 ? (2 * PTW + 3) / 4 + 1 : (XOFF + PWR + 3) / 4;  // 16-byte groups per input row
     constexpr bool UP = KS == 2;                     // rows = 4 * channel + parity class, stores into the (2 H x 2 W) output
-    constexpr int ITEMS3 = IMGS * PROWS * NG * (CB / 2);
-    constexpr int NI3 = KS == 1 ? 1 : (ITEMS3 + NTB - 1) / NTB;
     constexpr unsigned OOB = 0x80000000u;            // (>= num_records of the descriptor: the load returns zeros)
-    static_assert(NTB % 8 == 0, "a thread keeps its channel pair over its items");
-    unsigned ivo[NI3];
-    int idst[NI3], imask[NI3];
-    int idst1[S2 ? NI3 : 1];  // (stride 2: the odd-column plane's base; idst is the even-column plane's)
-    const int qpair = t & 7;
-    if constexpr (KS != 1 && !S2) {
-#pragma unroll
-        for (int j = 0; j < NI3; ++j) {
-            const int idx = t + j * NTB, rest = idx >> 3;
-            const int g = rest % NG, yy = rest / NG, il = yy / PH, y = yy - il * PH;
-            const int hi = ho0 - p.pad + y, wi = wo0 - bf3_gx0(KS) + 4 * g, img = img0 + il;
-            const bool ok = idx < ITEMS3 && img < nimg && (unsigned)hi < (unsigned)p.Hin && wi >= 0 && wi + 3 < p.Win;
-            ivo[j] = ok ? (unsigned)(((int64_t)img * p.in_img_stride + (int64_t)(2 * qpair) * HW + hi * p.Win + wi) * 4) : OOB;
-            idst[j] = ((il * PH + y) * PWR + 4 * g - XOFF) * PIXB + qpair * 4;  // pixel e of the group: + e * PIXB
-            int m = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m |= (idx < ITEMS3 && (unsigned)(4 * g + e - XOFF) < (unsigned)PWR) ? (1 << e) : 0;
-            imask[j] = m;
-        }
-    }
-    if constexpr (S2) {
-        // group g of input row y: pixels wi = 2 wo0 - 4 + 4 g + e.  e = 0, 2 are even columns 2 (wo0 + c): plane column
-        // c = 2 g - 2 + e / 2 (needed for c < PTW); e = 1, 3 are odd columns 2 (wo0 + c) - 1: c = 2 g - 1 + e / 2 (c <= PTW).
-        // Row y is input row 2 ho0 - 1 + y: y even = an odd row (plane row y / 2 <= PTH), y odd = an even row (plane row (y - 1) / 2).
-#pragma unroll
-        for (int j = 0; j < NI3; ++j) {
-            const int idx = t + j * NTB, rest = idx >> 3;
-            const int g = rest % NG, yy = rest / NG, il = yy / PROWS, y = yy - il * PROWS;
-            const int hi = 2 * ho0 - 1 + y, wi = 2 * wo0 - 4 + 4 * g, img = img0 + il;
-            const bool ok = idx < ITEMS3 && img < nimg && (unsigned)hi < (unsigned)p.Hin && wi >= 0 && wi + 3 < p.Win;
-            ivo[j] = ok ? (unsigned)(((int64_t)img * p.in_img_stride + (int64_t)(2 * qpair) * HW + hi * p.Win + wi) * 4) : OOB;
-            const int rp = (y & 1) ^ 1, prow = y >> 1;
-            const int pbase = (il * 4 + rp * 2) * PLANE + prow * PWR;
-            idst[j] = (pbase + 2 * g - 2) * PIXB + qpair * 4;           // even columns: e = 0 here, e = 2 one pixel on
-            idst1[j] = (pbase + PLANE + 2 * g - 1) * PIXB + qpair * 4;  // odd columns:  e = 1 here, e = 3 one pixel on
-            int m = 0;
-            if (idx < ITEMS3) {
-                m |= ((unsigned)(2 * g - 2) < (unsigned)PTW) ? 1 : 0;
-                m |= ((unsigned)(2 * g - 1) <= (unsigned)PTW) ? 2 : 0;
-                m |= ((unsigned)(2 * g - 1) < (unsigned)PTW) ? 4 : 0;
-                m |= ((unsigned)(2 * g) <= (unsigned)PTW) ? 8 : 0;
-            }
-            imask[j] = m;
-        }
-    }
+    Bf3GroupStager<KS, PH, PWR, IMGS, NTB, S2, !S2> gs;  // (1x1: unused; stride 2: the launcher insists on whole 16-channel chunks)
+    if constexpr (KS != 1) gs.setup(p, t, img0, nimg, ho0, wo0, p.pad);
     const __amdgpu_buffer_rsrc_t rB = bf3_rsrc(p.B);
     // 1x1: the patch is the output tile itself (no halo, maybe strided); NTB / NPIX thread groups share a pixel set and take
     // every (NTB / NPIX)-th chunk of the stage, all 8 channel pairs of each
@@ -238,11 +94,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
         dst1 = pix * PIXB;
     }
     float r0[NPI], r1[NPI];
-    v4i rv[NI3][2];
     auto load_patch = [&](int c) {
-        const int cbase = c * (CB * CS) * HW;
-        const int left = p.Cin - c * (CB * CS);  // channels this stage still has (ragged last chunk: the rest reads as zero)
         if constexpr (KS == 1) {
+            const int cbase = c * (CB * CS) * HW;
+            const int left = p.Cin - c * (CB * CS);  // channels this stage still has (ragged last chunk: the rest reads as zero)
 #pragma unroll
             for (int jj = 0; jj < CS / G1; ++jj)
 #pragma unroll
@@ -254,20 +109,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                     r1[jj * (CB / 2) + q] = p.B[ok1 ? o + HW : 0];
                 }
         } else {
-            const unsigned hw4 = (unsigned)HW * 4u;
-            const bool ok0 = 2 * qpair < left, ok1 = 2 * qpair + 1 < left;
-#pragma unroll
-            for (int j = 0; j < NI3; ++j) {
-                const unsigned v0 = ok0 ? ivo[j] : OOB, v1 = ok1 ? (ivo[j] | hw4 * 0u) + ((ivo[j] & OOB) ? 0u : hw4) : OOB;
-                rv[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)v0, cbase * 4, 0);
-                rv[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)v1, cbase * 4, 0);
-            }
+            gs.load(rB, c, HW, p.Cin);
         }
     };
     auto stage = [&](int c) -> uint32_t {  // returns the OR of the lower pieces this thread wrote (0: its values were bf16-exact)
-        uint32_t nz = 0;
-        const int left = p.Cin - c * (CB * CS);
         if constexpr (KS == 1) {
+            uint32_t nz = 0;
+            const int left = p.Cin - c * (CB * CS);
 #pragma unroll
             for (int jj = 0; jj < CS / G1; ++jj)
 #pragma unroll
@@ -278,28 +126,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                     uint32_t H, M, L;
                     split3_pair(v0, v1, H, M, L);
                     nz |= M | L;
-                    unsigned char* d = smem + (g1 + jj * G1) * (NPIX * PIXB) + dst1 + q * 4;
-                    *reinterpret_cast<uint32_t*>(d) = H;
-                    *reinterpret_cast<uint32_t*>(d + 32) = M;
-                    *reinterpret_cast<uint32_t*>(d + 64) = L;
+                    bf3_store_pieces(smem + (g1 + jj * G1) * (NPIX * PIXB) + dst1 + q * 4, H, M, L);
                 }
+            return nz;
         } else {
-#pragma unroll
-            for (int j = 0; j < NI3; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    uint32_t H, M, L;
-                    split3_pair(__int_as_float(rv[j][0][e]), __int_as_float(rv[j][1][e]), H, M, L);
-                    if ((imask[j] >> e) & 1) {  // (pixels of the group outside the patch - or items past the last - are not staged)
-                        nz |= M | L;
-                        unsigned char* d = S2 ? smem + ((e & 1) ? idst1[j] : idst[j]) + (e >> 1) * PIXB : smem + idst[j] + e * PIXB;
-                        *reinterpret_cast<uint32_t*>(d) = H;
-                        *reinterpret_cast<uint32_t*>(d + 32) = M;
-                        *reinterpret_cast<uint32_t*>(d + 64) = L;
-                    }
-                }
+            return gs.stage(smem);
         }
-        return nz;
     };
 
     // per-lane operand bases
@@ -384,24 +216,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                 if (r < KK * CS && (KS != 1 || c * CS + r < nch)) {  // (padding taps, and 1x1: chunks past the last one, issue nothing)
                     if (r + 1 < KK * CS) read_b(r + 1, bq[(r + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);  // (the reads stay AHEAD of this tap's MFMAs: left alone they sink to their use)
-                    bf16x8 a[TM][3];
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl) a[tm][pl] = __builtin_bit_cast(bf16x8, abuf[slot][tm][pl]);
-                    // smallest products first; consecutive MFMAs hit different accumulators
-#define IVLN_BF3_PROD(PA, PB)                                                                                       \
-    _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)              \
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][PA], bq[r & 1][tn][PB], acc[tm][tn], 0, 0, 0)
-                    if constexpr (!LITE) {
-                        IVLN_BF3_PROD(0, 2);
-                        IVLN_BF3_PROD(1, 1);
-                    }
-                    IVLN_BF3_PROD(2, 0);
-                    if constexpr (!LITE) IVLN_BF3_PROD(0, 1);
-                    IVLN_BF3_PROD(1, 0);
-                    IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+                    bf3_products<LITE ? BF3_THREE : BF3_SIX>(acc, abuf[slot], bq[r & 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // the slot just used receives the weights of DA taps ahead (the rotation closes over the stage: RP % DA == 0)
@@ -530,16 +345,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                 __builtin_amdgcn_sched_barrier(0);
                 load_a2(c + DA2, ab[c % DA2]);
                 __builtin_amdgcn_sched_barrier(0);
-#define IVLN_BF3_PROD(PA, PB)                           \
-    _Pragma("unroll") for (int e = 0; e < Q; ++e)       \
-        acc2[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], __builtin_bit_cast(bf16x8, bq[e][PB]), acc2[e], 0, 0, 0)
-                IVLN_BF3_PROD(0, 2);
-                IVLN_BF3_PROD(1, 1);
-                IVLN_BF3_PROD(2, 0);
-                IVLN_BF3_PROD(0, 1);
-                IVLN_BF3_PROD(1, 0);
-                IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+                bf3_products(acc2, a, bq);
             }
             // (the folded bn3 of the tile's channels: 8 x 16 bytes per lane, L2-resident after the first workgroups - asked for
             //  here, not before the K loop, because 32 more live registers there spill)
@@ -549,6 +355,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                 esc4[g] = __builtin_amdgcn_raw_buffer_load_b128(rS3, has_sc ? me3 * 4 : (int)OOB, g * 32, 0);
                 esh4[g] = __builtin_amdgcn_raw_buffer_load_b128(rH3, has_sh ? me3 * 4 : (int)OOB, g * 32, 0);
             }
+            // (not bf3_quad_store: operands in registers before the K loop, straight-line code between scalar-offset buffer stores)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int cs = (r & 3) + 8 * (r >> 2);
@@ -611,23 +418,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
                 const float2 t0 = *reinterpret_cast<const float2*>(T + ml * LDT + nl);
                 const float2 t1 = *reinterpret_cast<const float2*>(T + (ml + 1) * LDT + nl);
                 float4 v = make_float4(t0.x, t1.x, t0.y, t1.y);
-                if (p.scale) {
-                    const float sc = p.scale[co], sh = p.shift[co];
-                    v.x = fmaf(v.x, sc, sh), v.y = fmaf(v.y, sc, sh), v.z = fmaf(v.z, sc, sh), v.w = fmaf(v.w, sc, sh);
-                } else if (p.shift) {
-                    const float sh = p.shift[co];
-                    v.x += sh, v.y += sh, v.z += sh, v.w += sh;
-                }
-                if (p.residual) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.residual + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.accumulate) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.D + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                *reinterpret_cast<float4*>(p.D + addr) = v;
+                bf3_quad_store(p, v, addr, co);
             }
             __syncthreads();
             continue;
@@ -646,24 +437,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
             } else if (ok) {
                 v = *reinterpret_cast<const float4*>(T + ml * LDT + nl);
                 const int64_t addr = ((int64_t)img * p.Ctot + m) * p.HoWo + ho * p.Wout + wo;
-                const int me = p.grp_imgs > 0 ? (img / p.grp_imgs) * p.M + m : m;
-                if (p.scale) {
-                    const float sc = p.scale[me], sh = p.shift[me];
-                    v.x = fmaf(v.x, sc, sh), v.y = fmaf(v.y, sc, sh), v.z = fmaf(v.z, sc, sh), v.w = fmaf(v.w, sc, sh);
-                } else if (p.shift) {
-                    const float sh = p.shift[me];
-                    v.x += sh, v.y += sh, v.z += sh, v.w += sh;
-                }
-                if (p.residual) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.residual + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.accumulate) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.D + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                *reinterpret_cast<float4*>(p.D + addr) = v;
+                bf3_quad_store(p, v, addr, p.grp_imgs > 0 ? (img / p.grp_imgs) * p.M + m : m);
             }
             if (p.stat_partials) {  // (uniform) {count, mean, M2} of the 128 pixels a half-wave just stored
                 float cnt = ok ? 4.f : 0.f, sum = ok ? (v.x + v.y) + (v.z + v.w) : 0.f;
@@ -729,11 +503,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
     constexpr bool UP = KS == 2;
     static_assert(PTH * PTW == 32 * TN && (KS == 3 || KS == 2), "32 TN pixels per workgroup");
     constexpr int PH = PTH + KS - 1, PWR = PTW + KS - 1, NPIX = PH * PWR;
-    constexpr int XOFF = bf3_xoff(KS), NG = (XOFF + PWR + 3) / 4;
-    constexpr int ITEMS = PH * NG * (CB / 2), NI = (ITEMS + 63) / 64;
     constexpr int WREG = (NPIX * PIXB + 15) & ~15;  // bytes of a wave's patch region
     constexpr int LDT = 32 * TN + 4;
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -751,49 +522,10 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
     const int c0 = min(nch, wave * cpw), c1 = min(nch, c0 + cpw);
     unsigned char* const wsm = smem + wave * WREG;
 
-    // staging items of a LANE (the wave stages its own patch): (patch row, aligned 16-byte group, channel pair)
-    unsigned ivo[NI];
-    int idst[NI], imask[NI];
-    const int qpair = lane & 7;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int idx = lane + j * 64, rest = idx >> 3;
-        const int g = rest % NG, y = rest / NG;
-        const int hi = ho0 - (KS == 3 ? 1 : 0) + y, wi = wo0 - bf3_gx0(KS) + 4 * g;  // (pad 1 | the 2 x 2 window starts at the pixel itself)
-        const bool ok = idx < ITEMS && img0 < nimg && (unsigned)hi < (unsigned)p.Hin && wi >= 0 && wi + 3 < p.Win;
-        ivo[j] = ok ? (unsigned)(((int64_t)img0 * p.in_img_stride + (int64_t)(2 * qpair) * HW + hi * p.Win + wi) * 4) : OOB;
-        idst[j] = (y * PWR + 4 * g - XOFF) * PIXB + qpair * 4;
-        int m = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m |= (idx < ITEMS && (unsigned)(4 * g + e - XOFF) < (unsigned)PWR) ? (1 << e) : 0;
-        imask[j] = m;
-    }
+    // the wave stages its own patch: the items of a LANE (pad 1 | the 2 x 2 window starts at the pixel itself)
+    Bf3GroupStager<KS, PH, PWR, 1, 64, false, false> gs;
+    gs.setup(p, lane, img0, nimg, ho0, wo0, KS == 3 ? 1 : 0);
     const __amdgpu_buffer_rsrc_t rB = bf3_rsrc(p.B);
-    const unsigned hw4 = (unsigned)HW * 4u;
-    v4i rv[NI][2];
-    auto load_patch = [&](int c) {
-        const int so = c * CB * HW * 4;
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            rv[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)ivo[j], so, 0);
-            rv[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)((ivo[j] & OOB) ? OOB : ivo[j] + hw4), so, 0);
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t H, M, L;
-                split3_pair(__int_as_float(rv[j][0][e]), __int_as_float(rv[j][1][e]), H, M, L);
-                if ((imask[j] >> e) & 1) {
-                    unsigned char* d = wsm + idst[j] + e * PIXB;
-                    *reinterpret_cast<uint32_t*>(d) = H;
-                    *reinterpret_cast<uint32_t*>(d + 32) = M;
-                    *reinterpret_cast<uint32_t*>(d + 64) = L;
-                }
-            }
-    };
     int bbase[TN];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
@@ -822,7 +554,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
         for (int d = 0; d < DA; ++d)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) abuf[d][pl] = load_a(c0 * KK + d, pl);
-        load_patch(c0);
+        gs.load(rB, c0, HW, p.Cin);
 #ifdef BF3_TIMING
         __builtin_amdgcn_s_waitcnt(0);  // (timing build only: the prologue's round trip as a phase of its own)
         ts1 = lane == 0 ? wall_clock64() : 0ull;
@@ -831,7 +563,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
 #ifdef BF3_TIMING
             const unsigned long long tsa = lane == 0 ? wall_clock64() : 0ull;
 #endif
-            stage();
+            gs.stage(wsm);
 #ifdef BF3_TIMING
             __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
             t_stage += (lane == 0 ? wall_clock64() : 0ull) - tsa;
@@ -852,23 +584,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
                 const int slot = r % DA;
                 if (r + 1 < KK) read_b(r + 1, bq[(r + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                bf16x8 a[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) a[pl] = __builtin_bit_cast(bf16x8, abuf[slot][pl]);
-#define IVLN_BF3_PROD(PA, PB)                            \
-    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)    \
-        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], bq[r & 1][tn][PB], acc[tn], 0, 0, 0)
-                IVLN_BF3_PROD(0, 2);
-                IVLN_BF3_PROD(1, 1);
-                IVLN_BF3_PROD(2, 0);
-                IVLN_BF3_PROD(0, 1);
-                IVLN_BF3_PROD(1, 0);
-                IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+                bf3_products(acc, abuf[slot], bq[r & 1]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) abuf[slot][pl] = load_a(s0 + r + DA, pl);
-                if (r == (KK > 4 ? 1 : 0)) load_patch(min(c + 1, c1 - 1));  // (next chunk's patch: 7 | 3 taps of MFMA work before the staging pass reads it)
+                if (r == (KK > 4 ? 1 : 0)) gs.load(rB, min(c + 1, c1 - 1), HW, p.Cin);  // (next chunk's patch: 7 | 3 taps of MFMA work before the staging pass reads it)
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -879,11 +599,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
 #endif
     __syncthreads();  // every wave is done reading its patch
     float* const red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + tn * 32 + l31] = acc[tn][r];
+    bf3_red_put<LDT>(red, wave, half, l31, acc);
     __syncthreads();
     if constexpr (UP) {
         // 8 channels x 2 rows of the 2 x 2 blocks x 16 TN pixel pairs: GEMM rows 4 c + 2 a (b = 0) and + 1 (b = 1) at two
@@ -893,33 +609,12 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
             const int ml = 2 * r, nl = 2 * j;
             const int ph = nl / PTW, pw = nl % PTW;
             const int ho = ho0 + ph, wo = wo0 + pw;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {  // fixed order
-                const float2 u0 = *reinterpret_cast<const float2*>(red + (w * 32 + ml) * LDT + nl);
-                const float2 u1 = *reinterpret_cast<const float2*>(red + (w * 32 + ml + 1) * LDT + nl);
-                v.x += u0.x, v.y += u1.x, v.z += u0.y, v.w += u1.y;
-            }
+            const float2 u0 = bf3_red_sum<NW, LDT, float2>(red + ml * LDT + nl), u1 = bf3_red_sum<NW, LDT, float2>(red + (ml + 1) * LDT + nl);
+            float4 v = make_float4(u0.x, u1.x, u0.y, u1.y);
             if (m0 + ml < p.M && img0 < nimg && ho < p.Hout && wo < p.Wout) {
                 const int co = (m0 + ml) >> 2, a = r & 1;
                 const int64_t addr = (((int64_t)img0 * p.Ctot + co) * (2 * p.Hout) + 2 * ho + a) * (2 * p.Wout) + 2 * wo;
-                if (p.scale) {
-                    const float sc = p.scale[co], sh = p.shift[co];
-                    v.x = fmaf(v.x, sc, sh), v.y = fmaf(v.y, sc, sh), v.z = fmaf(v.z, sc, sh), v.w = fmaf(v.w, sc, sh);
-                } else if (p.shift) {
-                    const float sh = p.shift[co];
-                    v.x += sh, v.y += sh, v.z += sh, v.w += sh;
-                }
-                if (p.residual) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.residual + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.accumulate) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.D + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                *reinterpret_cast<float4*>(p.D + addr) = v;
+                bf3_quad_store(p, v, addr, co);
             }
         }
     } else if (t < 32 * 8 * TN) {
@@ -927,32 +622,10 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
         const int m = m0 + ml, nl = 4 * c4;
         const int ph = nl / PTW, pw = nl % PTW;
         const int ho = ho0 + ph, wo = wo0 + pw;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {  // fixed order: the sum does not depend on the run
-            const float4 u = *reinterpret_cast<const float4*>(red + (w * 32 + ml) * LDT + nl);
-            v.x += u.x, v.y += u.y, v.z += u.z, v.w += u.w;
-        }
+        float4 v = bf3_red_sum<NW, LDT, float4>(red + ml * LDT + nl);
         if (m < p.M && img0 < nimg && ho < p.Hout && wo < p.Wout) {
             const int64_t addr = ((int64_t)img0 * p.Ctot + m) * p.HoWo + ho * p.Wout + wo;
-            const int me = p.grp_imgs > 0 ? (img0 / p.grp_imgs) * p.M + m : m;
-            if (p.scale) {
-                const float sc = p.scale[me], sh = p.shift[me];
-                v.x = fmaf(v.x, sc, sh), v.y = fmaf(v.y, sc, sh), v.z = fmaf(v.z, sc, sh), v.w = fmaf(v.w, sc, sh);
-            } else if (p.shift) {
-                const float sh = p.shift[me];
-                v.x += sh, v.y += sh, v.z += sh, v.w += sh;
-            }
-            if (p.residual) {
-                const float4 rr = *reinterpret_cast<const float4*>(p.residual + addr);
-                v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-            }
-            if (p.accumulate) {
-                const float4 rr = *reinterpret_cast<const float4*>(p.D + addr);
-                v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-            }
-            if (p.relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-            *reinterpret_cast<float4*>(p.D + addr) = v;
+            bf3_quad_store(p, v, addr, p.grp_imgs > 0 ? (img0 / p.grp_imgs) * p.M + m : m);
         }
     }
 #ifdef BF3_TIMING
@@ -974,12 +647,8 @@ int launch_bf3_ks_tile(const ivln_gemm_desc& d, hipStream_t s, const unsigned ch
     constexpr int NPIX = (PTH + KS - 1) * (PTW + KS - 1), WREG = (NPIX * PIXB + 15) & ~15, RED = 8 * 32 * (32 * TN + 4) * 4;
     constexpr size_t lds = (size_t)(8 * WREG > RED ? 8 * WREG : RED);
     static_assert(lds <= 160 * 1024, "patch regions do not fit");
-    auto kern = k_conv_bf3_ks<PTH, PTW, TN, KS>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-        attr_done = true;
-    }
+    constexpr auto kern = k_conv_bf3_ks<PTH, PTW, TN, KS>;
+    if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     const int tiles_w = d.Wout / PTW, tiles_h = d.Hout / PTH;
     dim3 grid(tiles_w * tiles_h * nimg, (d.M + 31) / 32, 1);
     IVLN_LAUNCH_FAMILY_NAMED("k_conv_bf3_ks", kern, grid, dim3(512), lds, s, d, a_split, (long long)grp_bytes, tiles_w, tiles_h, nimg);
@@ -1004,9 +673,8 @@ int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_p
     }
     if (d.Wout != 8 && d.Wout != 16 && d.Wout != 32) return IVLN_E_UNSUPPORTED;
     const int64_t wgs = (int64_t)(d.N / 64) * ((d.M + 31) / 32);
-    // 32-pixel tiles where 64-pixel ones leave half of the CUs without a workgroup; IVLN_BF3_KS_TN = 1 | 2 pins one (tuning)
-    constexpr int tn_env = 0;
-    const bool small = tn_pin ? tn_pin == 1 : (tn_env ? tn_env == 1 : 2 * wgs <= ivln_cu_count());
+    // 32-pixel tiles where 64-pixel ones leave half of the CUs without a workgroup; tn_pin = 1 | 2 pins one (tile_override 14 | 15)
+    const bool small = tn_pin ? tn_pin == 1 : 2 * wgs <= ivln_cu_count();
     const int pth = (small ? 32 : 64) / d.Wout;
     if (d.Hout % pth != 0 || (d.in_img_stride & 3) || (((uintptr_t)d.B) & 15)) return IVLN_E_UNSUPPORTED;
     if ((int64_t)nimg * d.in_img_stride * 4 >= (int64_t)1 << 31) return IVLN_E_UNSUPPORTED;  // byte offsets of the buffer loads
@@ -1047,13 +715,10 @@ template <int NW, bool U8>
 __global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_desc p, const unsigned char* a_split, int tiles_w, int tiles_h, int nimg) {
     constexpr int KS = 7, KK = KS * KS, KKP = bf3_taps_padded(KS), DA = KS, PTH = 4, PTW = 8, NTB = 64 * NW;
     constexpr int PH = PTH + KS - 1, PWR = PTW + KS - 1, NPIX = PH * PWR;
-    constexpr int XOFF = bf3_xoff(KS), NG = (XOFF + PWR + 3) / 4;
-    constexpr int ITEMS = PH * NG * (CB / 2), NI = U8 ? 1 : (ITEMS + 63) / 64;
     constexpr int NPJ = (NPIX + 63) / 64;  // (U8: patch pixels per lane)
     constexpr int WREG = (NPIX * PIXB + 15) & ~15;
     constexpr int LDT = 32 + 4;
     constexpr int NPL = U8 ? 1 : 3;  // pieces of the activations
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(KK % DA == 0, "the weight rotation closes over a chunk");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -1070,56 +735,16 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_d
     const int niter = wave < nch ? (nch - wave + NW - 1) / NW : 0;  // chunks wave, wave + NW, ...
     unsigned char* const wsm = smem + wave * WREG;
 
-    // f32 input: staging items of a lane = (patch row, aligned 16-byte group, channel pair), as in k_conv_bf3_ks
-    unsigned ivo[NI];
-    int idst[NI], imask[NI];
-    const int qpair = lane & 7;
-    if constexpr (!U8) {
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int idx = lane + j * 64, rest = idx >> 3;
-            const int g = rest % NG, y = rest / NG;
-            const int hi = ho0 - KS / 2 + y, wi = wo0 - bf3_gx0(KS) + 4 * g;
-            const bool ok = idx < ITEMS && img0 < nimg && (unsigned)hi < (unsigned)p.Hin && wi >= 0 && wi + 3 < p.Win;
-            ivo[j] = ok ? (unsigned)(((int64_t)img0 * p.in_img_stride + (int64_t)(2 * qpair) * HW + hi * p.Win + wi) * 4) : OOB;
-            idst[j] = (y * PWR + 4 * g - XOFF) * PIXB + qpair * 4;
-            int m = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m |= (idx < ITEMS && (unsigned)(4 * g + e - XOFF) < (unsigned)PWR) ? (1 << e) : 0;
-            imask[j] = m;
-        }
-    }
+    // f32 input: the wave stages its own patch, as in k_conv_bf3_ks (a ragged last chunk - 14 channels - reads the rest as zero)
+    Bf3GroupStager<KS, PH, PWR, 1, 64> gs;
+    if constexpr (!U8) gs.setup(p, lane, img0, nimg, ho0, wo0, KS / 2);
     const __amdgpu_buffer_rsrc_t rB = bf3_rsrc(p.B);
-    const unsigned hw4 = (unsigned)HW * 4u;
-    v4i rv[NI][2];
     auto load_patch = [&](int c) {
-        if constexpr (!U8) {
-            const int so = c * CB * HW * 4;
-            const int left = p.Cin - c * CB;  // (a ragged last chunk - 14 channels - reads its missing channels as zero)
-            const bool ok0 = 2 * qpair < left, ok1 = 2 * qpair + 1 < left;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const bool in = !(ivo[j] & OOB);
-                rv[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)(in && ok0 ? ivo[j] : OOB), so, 0);
-                rv[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)(in && ok1 ? ivo[j] + hw4 : OOB), so, 0);
-            }
-        }
+        if constexpr (!U8) gs.load(rB, c, HW, p.Cin);
     };
     auto stage = [&]() {
         if constexpr (!U8) {
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    uint32_t H, M, L;
-                    split3_pair(__int_as_float(rv[j][0][e]), __int_as_float(rv[j][1][e]), H, M, L);
-                    if ((imask[j] >> e) & 1) {
-                        unsigned char* d = wsm + idst[j] + e * PIXB;
-                        *reinterpret_cast<uint32_t*>(d) = H;
-                        *reinterpret_cast<uint32_t*>(d + 32) = M;
-                        *reinterpret_cast<uint32_t*>(d + 64) = L;
-                    }
-                }
+            gs.stage(wsm);
         } else {
             // a patch pixel per lane and round: its two bytes -> the 16-channel record of the first piece (32 bytes: word q =
             // channels 2 q, 2 q + 1).  Outside the image (the conv's zero padding): zeros, no label matches.
@@ -1161,9 +786,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_d
         const int qc = min(q, q_last), i = qc / KK, r = qc - i * KK;
         return __builtin_amdgcn_raw_buffer_load_b128(rA, (((wave + i * NW) * KKP + r) * 3 + pl) * 1024 + lane * 16, 0, 0);
     };
-    f32x16 acc;
+    f32x16 acc[1];  // (one 32-pixel tile)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
 
     if (niter > 0) {
         v4i abuf[DA][3];
@@ -1175,31 +800,19 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_d
         for (int i = 0; i < niter; ++i) {
             stage();
             const int s0 = i * KK;
-            auto read_b = [&](int r, bf16x8 (&b)[3]) {
+            auto read_b = [&](int r, bf16x8 (&b)[1][3]) {
                 const int kh = r / KS, kw = r - kh * KS, toff = (kh * PWR + kw) * PIXB;
 #pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) b[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const v4i*>(wsm + bbase + toff + pl * 32));
+                for (int pl = 0; pl < NPL; ++pl) b[0][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const v4i*>(wsm + bbase + toff + pl * 32));
             };
-            bf16x8 bq[2][3];
+            bf16x8 bq[2][1][3];
             read_b(0, bq[0]);
 #pragma unroll
             for (int r = 0; r < KK; ++r) {
                 const int slot = r % DA;
                 if (r + 1 < KK) read_b(r + 1, bq[(r + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                bf16x8 a[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) a[pl] = __builtin_bit_cast(bf16x8, abuf[slot][pl]);
-#define IVLN_BF3_PROD(PA, PB) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], bq[r & 1][PB], acc, 0, 0, 0)
-                if constexpr (!U8) {
-                    IVLN_BF3_PROD(0, 2);
-                    IVLN_BF3_PROD(1, 1);
-                }
-                IVLN_BF3_PROD(2, 0);
-                if constexpr (!U8) IVLN_BF3_PROD(0, 1);
-                IVLN_BF3_PROD(1, 0);
-                IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+                bf3_products<U8 ? BF3_THREE : BF3_SIX>(acc, abuf[slot], bq[r & 1]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) abuf[slot][pl] = load_a(s0 + r + DA, pl);
@@ -1211,21 +824,15 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv7_pool_bf3(const ivln_gemm_d
     // ---- the partial tiles meet in LDS: red[wave][32 channels][32 pixels (+4)] over the patch regions; then the CBRA tail ----
     __syncthreads();
     float* const red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + l31] = acc[r];
+    bf3_red_put<LDT>(red, wave, half, l31, acc);
     __syncthreads();
     const int Hp = p.Hout >> 1, Wp = p.Wout >> 1;
     for (int idx = t; idx < 32 * (PTH / 2) * (PTW / 2); idx += NTB) {
         const int ml = idx >> 3, pp = idx & 7, py = pp >> 2, px = pp & 3;  // (PTH / 2) x (PTW / 2) = 2 x 4 windows per channel
         const int m = m0 + ml;
-        float2 tt = make_float2(0.f, 0.f), uu = make_float2(0.f, 0.f);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {  // fixed order: the sum does not depend on the run
-            const float* rp = red + (w * 32 + ml) * LDT + (2 * py) * PTW + 2 * px;
-            const float2 t2 = *reinterpret_cast<const float2*>(rp), u2 = *reinterpret_cast<const float2*>(rp + PTW);
-            tt.x += t2.x, tt.y += t2.y, uu.x += u2.x, uu.y += u2.y;
-        }
-        if (m < p.M && img0 < nimg) {
+        const float* const rp = red + ml * LDT + (2 * py) * PTW + 2 * px;  // the window's upper row; the lower one PTW on
+        const float2 tt = bf3_red_sum<NW, LDT, float2>(rp), uu = bf3_red_sum<NW, LDT, float2>(rp + PTW);
+        if (m < p.M && img0 < nimg) {  // (not bf3_quad_store: four outputs become ONE pooled value, in k_scale_shift_relu_avgpool2's order)
             const float sc = p.scale[m], sh = p.shift[m];
             const float a = fmaxf(fmaf(tt.x, sc, sh), 0.f), b = fmaxf(fmaf(tt.y, sc, sh), 0.f);
             const float c2 = fmaxf(fmaf(uu.x, sc, sh), 0.f), d = fmaxf(fmaf(uu.y, sc, sh), 0.f);
@@ -1239,12 +846,8 @@ int launch_conv7_pool(const ivln_gemm_desc& d, hipStream_t s, int nimg) {
     constexpr int WREG = ((4 + 6) * (8 + 6) * PIXB + 15) & ~15, RED = 32 * 36 * 4;
     constexpr size_t lds = (size_t)NW * (WREG > RED ? WREG : RED);
     static_assert(lds <= 160 * 1024, "patch regions do not fit");
-    auto kern = k_conv7_pool_bf3<NW, U8>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-        attr_done = true;
-    }
+    constexpr auto kern = k_conv7_pool_bf3<NW, U8>;
+    if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     const int tiles_w = d.Wout / 8, tiles_h = d.Hout / 4;
     dim3 grid(tiles_w * tiles_h * nimg, (d.M + 31) / 32, 1);
     IVLN_LAUNCH_FAMILY_NAMED("k_conv7_pool_bf3", kern, grid, dim3(64 * NW), lds, s, d, (const unsigned char*)d.A_split, tiles_w, tiles_h, nimg);
@@ -1393,20 +996,11 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
                 __builtin_amdgcn_sched_barrier(0);
 #endif
                 if (c < c1) {
-#define IVLN_BF3_PROD(PA, PB)                            \
-    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)    \
-        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], __builtin_bit_cast(bf16x8, bq[tn][PB]), acc[tn], 0, 0, 0)
 #ifdef BF3_PROBE_NO_MFMA  // (... and without its matrix work: one product of the six)
-                    IVLN_BF3_PROD(0, 0);
+                    bf3_products<BF3_ONE>(acc, a[0], a[1], a[2], bq);
 #else
-                    IVLN_BF3_PROD(0, 2);
-                    IVLN_BF3_PROD(1, 1);
-                    IVLN_BF3_PROD(2, 0);
-                    IVLN_BF3_PROD(0, 1);
-                    IVLN_BF3_PROD(1, 0);
-                    IVLN_BF3_PROD(0, 0);
+                    bf3_products(acc, a[0], a[1], a[2], bq);
 #endif
-#undef IVLN_BF3_PROD
                 }
 #ifdef BF3_TIMING
                 __builtin_amdgcn_sched_barrier(0);
@@ -1471,6 +1065,7 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
         const bool has_res = p.residual != nullptr, has_sc = p.scale != nullptr, has_sh = p.shift != nullptr;
         const float relu_lo = p.relu ? 0.f : -__builtin_huge_valf();
         const bool res_post = p.residual_after_relu != 0;
+        // (not bf3_quad_store: straight-line code between scalar-offset buffer stores, BF3_STORE_GUARD behind each)
         v4i rres[16];
         float esc[16], esh[16];
 #pragma unroll
@@ -1506,45 +1101,26 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
         // the eight waves' partial tiles meet in LDS as below; an item = (channel of the tile, a, pixel pair): rows 4 c + 2 a and + 1
         // at two horizontally adjacent class-grid pixels = four consecutive floats of output row 2 ho + a
         float* const red = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + tn * 32 + l31] = acc[tn][r];
+        bf3_red_put<LDT>(red, wave, half, l31, acc);
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int item = t + it * 512, r = item >> 6, j = item & 63;  // 16 (channel, a) x 64 pixel pairs
             const int ml = 2 * r, nl = 2 * j, n = n0 + nl;
             const int e0 = nl & 3, q = nl >> 2;  // tile e, column q holds pixel 4 q + e
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {  // fixed order
-                const float* r0 = red + (w * 32 + ml) * LDT + q;
-                const float* r1 = r0 + LDT;
-                v.x += r0[e0 * 32], v.y += r1[e0 * 32], v.z += r0[(e0 + 1) * 32], v.w += r1[(e0 + 1) * 32];
-            }
+            const float* const r0 = red + ml * LDT + q + e0 * 32;  // rows ml and ml + 1, tiles e0 and e0 + 1
+            const float2 u0 = bf3_red_sum<NW, LDT, float2, 32>(r0), u1 = bf3_red_sum<NW, LDT, float2, 32>(r0 + LDT);
+            float4 v = make_float4(u0.x, u1.x, u0.y, u1.y);
             if (m0 + ml < p.M && n < p.N) {
                 const int img = n / HW, pp = n - img * HW;
                 const int ho = pp / p.Wout, wo = pp - ho * p.Wout;
                 const int co = (m0 + ml) >> 2, a = r & 1;
                 const int64_t addr = (((int64_t)img * p.Ctot + co) * (2 * p.Hout) + 2 * ho + a) * (2 * p.Wout) + 2 * wo;
-                if (p.scale) {
-                    const float sc = p.scale[co], sh = p.shift[co];
-                    v.x = fmaf(v.x, sc, sh), v.y = fmaf(v.y, sc, sh), v.z = fmaf(v.z, sc, sh), v.w = fmaf(v.w, sc, sh);
-                } else if (p.shift) {
-                    const float sh = p.shift[co];
-                    v.x += sh, v.y += sh, v.z += sh, v.w += sh;
-                }
-                if (p.residual) {
-                    const float4 rr = *reinterpret_cast<const float4*>(p.residual + addr);
-                    v.x += rr.x, v.y += rr.y, v.z += rr.z, v.w += rr.w;
-                }
-                if (p.relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                *reinterpret_cast<float4*>(p.D + addr) = v;
+                bf3_quad_store(p, v, addr, co);  // (`accumulate` never set here: the launcher declines it)
             }
         }
     } else {
+    // (not bf3_quad_store: the operands are requested BEFORE the barrier, and the absent residual stays a branch - see the -0 remark)
     constexpr int ITEMS = 2;  // 32 channels x 32 pixel quads = 1024 items over the workgroup's 512 threads
     v4i rres[ITEMS];
     float esc[ITEMS], esh[ITEMS];
@@ -1566,21 +1142,12 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) request(it);
     float* const red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + tn * 32 + l31] = acc[tn][r];
+    bf3_red_put<LDT>(red, wave, half, l31, acc);
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int item = t + it * 512, ml = item >> 5, q = item & 31;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {  // fixed order; tile e, column q = pixel 4 q + e
-            const float* rr = red + (w * 32 + ml) * LDT + q;
-            v.x += rr[0], v.y += rr[32], v.z += rr[64], v.w += rr[96];
-        }
+        float4 v = bf3_red_sum<NW, LDT, float4, 32>(red + ml * LDT + q);  // tile e, column q = pixel 4 q + e
         if (eoff[it] >= 0) {
             const int64_t addr = eoff[it];
             const float sc = esc[it], sh = esh[it];
@@ -1628,25 +1195,21 @@ int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin =
     if (d.grp_imgs > 0 && ((int64_t)d.grp_imgs * d.HoWo) % 128 != 0) return IVLN_E_UNSUPPORTED;  // a tile's pixels share one weight set
     const int nch = d.Cin / CB;
     // wave tiles (no K split) up to 16 chunks, K split over the 8 waves from 32 (in between - 272 ... 496 channels - the K-split
-    // form with short slices); IVLN_BF3_1X1_FORM = ks | wt pins one (tuning)
-    constexpr const char* form_env = nullptr;
+    // form with short slices); form_pin = 0 | 1 pins one (tile_override 12 | 13)
     bool wt = nch <= 16;
     // (32 chunks over MANY pixels - 256 x 16384 x 512, layer 3's first reduction at 8 + 8 images - would be four rounds of one
     //  K-split workgroup per CU: the wave tiles take it, 43.6 against 51.5 us on the tiled 1x1 form and 52.1 K-split, tools/conv_cfg_sweep.py)
-    constexpr int maxwg0 = 2;
-    if (nch == 32 && (int64_t)((d.N + 127) / 128) * ((d.M + 31) / 32) > maxwg0 * (int64_t)ivln_cu_count()) wt = true;
-    if (form_env) wt = form_env[0] == 'w';
+    if (nch == 32 && (int64_t)((d.N + 127) / 128) * ((d.M + 31) / 32) > 2 * (int64_t)ivln_cu_count()) wt = true;
     if (form_pin >= 0) wt = form_pin == 1;
     if (wt && nch > 64) wt = false;
     if (wt && d.accumulate) return IVLN_E_UNSUPPORTED;  // (the wave-tile epilogue is straight-line code: no D += form)
     const int64_t mtiles = (d.M + 31) / 32;
     const int64_t wgs = wt ? (int64_t)((d.N + 511) / 512) * mtiles : (int64_t)((d.N + 127) / 128) * mtiles;
-    constexpr int maxwg_env = 2;  // tuning: rounds of one workgroup per CU
     if ((d.N + 127) / 128 > 65535) return IVLN_E_UNSUPPORTED;
     if (mode == 0) {
         // (measured inside RedNet: wins at 128 ... 512 workgroups - 256 x 4096 x 1024 35.7 -> 28 us, 256 x 2048 x 1024 28.4 -> 21.6 -,
         //  loses at 64 - 512 x 512 x 2048 - and at 1024 - 256 x 16384 x 512, four rounds of one workgroup per CU)
-        if (!wt && (d.Cin < 32 * CB || wgs > maxwg_env * (int64_t)ivln_cu_count() || wgs < ivln_cu_count() / 2)) return IVLN_E_UNSUPPORTED;
+        if (!wt && (d.Cin < 32 * CB || wgs > 2 * (int64_t)ivln_cu_count() || wgs < ivln_cu_count() / 2)) return IVLN_E_UNSUPPORTED;
         if (wt && wgs < ivln_cu_count()) return IVLN_E_UNSUPPORTED;  // (too few wave tiles to fill the chip: the tiled GEMMs split K)
     }
     d.splits = 1;
@@ -1658,11 +1221,7 @@ int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin =
         IVLN_LAUNCH_FAMILY(k_conv1x1_bf3_ks<true>, grid, dim3(256), lds, s, d, a, gb);
     } else {
         constexpr size_t lds = (size_t)8 * 32 * (128 + 4) * 4;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute((const void*)k_conv1x1_bf3_ks<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-            attr_done = true;
-        }
+        if (bf3_set_lds<k_conv1x1_bf3_ks<false>>(lds) != IVLN_OK) return IVLN_E_HIP;
         dim3 grid((unsigned)mtiles, (unsigned)((d.N + 127) / 128), 1);
         IVLN_LAUNCH_FAMILY(k_conv1x1_bf3_ks<false>, grid, dim3(512), lds, s, d, a, gb);
     }
@@ -1700,12 +1259,8 @@ int launch_bf3(const ivln_gemm_desc& d, hipStream_t s, const unsigned char* a_sp
     if constexpr (lds > 160 * 1024) {
         return IVLN_E_UNSUPPORTED;  // (a stride-2 tile whose planes do not fit: the dispatcher picks another)
     } else {
-    auto kern = k_conv_bf3<KS, TM, WM, WN, PTH, PTW, IMGS, DA, false, ST>;
-    static bool attr_done = false;  // (idempotent; a race only repeats the call)
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-        attr_done = true;
-    }
+    constexpr auto kern = k_conv_bf3<KS, TM, WM, WN, PTH, PTW, IMGS, DA, false, ST>;
+    if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     const int tiles_w = (d.Wout + PTW - 1) / PTW, tiles_h = (d.Hout + PTH - 1) / PTH;
     const int groups = (nimg + IMGS - 1) / IMGS;
     dim3 grid(tiles_w * tiles_h * groups, (d.M + BM - 1) / BM, d.splits);
@@ -1721,12 +1276,8 @@ int launch_bf3_fused(const ivln_gemm_desc& d, hipStream_t s, const unsigned char
     static_assert(NTB == 256, "four waves");
     constexpr int NPIX = (PTH + 2) * (PTW + 2);
     constexpr size_t ybytes = (size_t)BM * (BN + 4) * 4, lds = (size_t)NPIX * PIXB > ybytes ? (size_t)NPIX * PIXB : ybytes;
-    auto kern = k_conv_bf3<KS, TM, WM, WN, PTH, PTW, 1, DA, true>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-        attr_done = true;
-    }
+    constexpr auto kern = k_conv_bf3<KS, TM, WM, WN, PTH, PTW, 1, DA, true>;
+    if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     const int tiles_w = d.Wout / PTW, tiles_h = d.Hout / PTH;
     dim3 grid(tiles_w * tiles_h * nimg, 1, 1);
     const int nch = d.Cin / CB;
@@ -1808,6 +1359,9 @@ int launch_bf3_ks(const ivln_gemm_desc& d, hipStream_t s, const unsigned char* a
 
 // stride-2 3x3 (k_conv_bf3<..., ST = 2>): the tiles whose four phase planes fit the LDS
 int launch_bf3_s2(const ivln_gemm_desc& d, hipStream_t s, const unsigned char* a, int64_t gb, int nimg, int cfg, int cps) {
+    // (k_conv_bf3<..., ST = 2> stages without the ragged-chunk test - Bf3GroupStager<..., RAGGED = false>: a last chunk of fewer
+    //  than 16 channels would read the next image's)
+    if (d.Cin % CB != 0) return IVLN_E_UNSUPPORTED;
     switch (cfg) {
         case 2: return launch_bf3_px<3, 1, 2, 4, 3, 2>(d, s, a, gb, nimg, cps);   // 64 x 256
         case 3: return launch_bf3_px<3, 2, 2, 4, 3, 2>(d, s, a, gb, nimg, cps);   // 128 x 256
@@ -2029,18 +1583,7 @@ __global__ __launch_bounds__(64 * WM * WN, XE ? 3 : 1) void k_wgrad_bf3(const iv
             for (int ks = 0; ks < 8; ++ks) {
                 if (ks + 1 < 8) read_ab(ks + 1, aq[(ks + 1) & 1], bq[(ks + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-#define IVLN_BF3_PROD(PA, PB)                                                                                       \
-    _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)              \
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[ks & 1][tm][PA], bq[ks & 1][tn][PB], acc[tm][tn], 0, 0, 0)
-                if constexpr (!LITE) {
-                    IVLN_BF3_PROD(0, 2);
-                    IVLN_BF3_PROD(1, 1);
-                }
-                IVLN_BF3_PROD(2, 0);
-                if constexpr (!LITE) IVLN_BF3_PROD(0, 1);
-                IVLN_BF3_PROD(1, 0);
-                IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+                bf3_products<LITE ? BF3_THREE : BF3_SIX>(acc, aq[ks & 1], bq[ks & 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -2089,12 +1632,8 @@ int launch_wgrad_bf3(const ivln_gemm_desc& d, hipStream_t s, int nimg, int strip
     constexpr int PRT = IMS * (ROWS + 6), XP = ((W + 6) / 2 + 1) | 1, NCIB = (BN + 48) / 49 + 1;
     constexpr size_t lds = (size_t)3 * BM * 272 + (size_t)(XE ? 2 : 6) * NCIB * PRT * XP * 4;
     static_assert(lds <= 160 * 1024, "strip does not fit");
-    auto kern = k_wgrad_bf3<TM, WM, WN, W, XE>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IVLN_E_HIP;
-        attr_done = true;
-    }
+    constexpr auto kern = k_wgrad_bf3<TM, WM, WN, W, XE>;
+    if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     dim3 grid((d.N + BN - 1) / BN, (d.M + BM - 1) / BM, d.splits);
     IVLN_LAUNCH_FAMILY_NAMED("k_wgrad_bf3", kern, grid, dim3(64 * WM * WN), lds, s, d, nimg, strips, sps);
     return IVLN_OK;
@@ -2207,19 +1746,7 @@ __global__ __launch_bounds__(256, 2) void k_conv7s2_bf3(const ivln_gemm_desc p, 
             for (int e = 0; e < TN; ++e)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bq[e][0][i] = (int)Hh[e + i], bq[e][1][i] = (int)Mm[e + i], bq[e][2][i] = (int)Ll[e + i];
-            bf16x8 a[3];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) a[pl] = __builtin_bit_cast(bf16x8, ab[s % 3][pl]);
-#define IVLN_BF3_PROD(PA, PB)                            \
-    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)    \
-        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA], __builtin_bit_cast(bf16x8, bq[tn][PB]), acc[tn], 0, 0, 0)
-            IVLN_BF3_PROD(0, 2);
-            IVLN_BF3_PROD(1, 1);
-            IVLN_BF3_PROD(2, 0);
-            IVLN_BF3_PROD(0, 1);
-            IVLN_BF3_PROD(1, 0);
-            IVLN_BF3_PROD(0, 0);
-#undef IVLN_BF3_PROD
+            bf3_products(acc, ab[s % 3], bq);
         }
     }
     // ---- epilogue (the wave-tile 1x1 kernel's): register r of the four tiles = channel (r & 3) + 8 (r >> 2) + 4 half at pixels
@@ -2347,21 +1874,24 @@ extern "C" int ivln_conv_bf3_stamps(unsigned long long* host, int n) {
 #endif
 
 int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
-    constexpr bool disabled = false;  // A/B switch
-    if (!d.A_split || (disabled && !force)) return IVLN_E_UNSUPPORTED;
-    if (d.pool2) {  // a map-CNN block as one launch (k_conv7_pool_bf3): K split over the waves, the CBRA tail in the epilogue
-        const int rc = bf3_conv7_pool_launch(d, s);
-        if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[1];
+    if (!d.A_split) return IVLN_E_UNSUPPORTED;
+    // every launch below returns through here: the tally of ivln_conv_split_counters / _kinds, and the caller's stat_tiles
+    // (st < 0: the path does not know stat_partials' caller and leaves the word alone)
+    auto done = [&](int rc, double flops, int kind, int st) {
+        if (rc == IVLN_OK) {
+            g_bf3_flops += flops, ++g_bf3_launches, ++g_bf3_kind[kind];
+            if (st >= 0 && d.stat_tiles) *d.stat_tiles = st;
+        }
         return rc;
+    };
+    const double flops = 2.0 * d.M * (double)d.N * d.K;  // algorithmic FLOPs of the conv
+    if (d.pool2) {  // a map-CNN block as one launch (k_conv7_pool_bf3): K split over the waves, the CBRA tail in the epilogue
+        return done(bf3_conv7_pool_launch(d, s), flops, 1, -1);
     }
     const int KS = d.bmode == BMODE_CONV1X1 ? 1 : conv_ks(d.bmode);
     if ((KS != 1 && KS != 2 && KS != 3 && KS != 7) || d.amode != AMODE_MK || d.dil != 1) return IVLN_E_UNSUPPORTED;
-    if (KS == 7 && d.stride == 2) {  // RedNet's stems: A_split is the image of ivln_conv_stem_split_weights_f32 (the caller's contract)
-        const int rc = bf3_stem_launch(d, s);
-        if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[0];
-        if (rc == IVLN_OK && d.stat_tiles) *d.stat_tiles = 0;
-        return rc;
-    }
+    // RedNet's stems: A_split is the image of ivln_conv_stem_split_weights_f32 (the caller's contract)
+    if (KS == 7 && d.stride == 2) return done(bf3_stem_launch(d, s), flops, 0, 0);
     // (the 2 x 2 window only as the stacked transposed-conv classes; a 1x1 conv may store them too: the 2 x 2 stride-2 upsampling convs)
     const bool up1 = KS == 1 && d.dmode == DMODE_NCHW_UP2X4;
     if (!up1 && d.dmode != (KS == 2 ? DMODE_NCHW_UP2X4 : DMODE_NCHW)) return IVLN_E_UNSUPPORTED;
@@ -2373,12 +1903,11 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
             return IVLN_E_UNSUPPORTED;
         const int ovu = d.tile_override;
         const int rc = bf3_1x1_ks_launch(d, s, (force || ovu == 11 || ovu == 12 || ovu == 13) ? 1 : 0, ovu == 12 ? 0 : (ovu == 13 ? 1 : -1));
-        if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[d.Cin / CB <= 16 ? 3 : 2];
-        return rc;
+        return done(rc, flops, d.Cin / CB <= 16 ? 3 : 2, -1);
     }
-    // algorithmic FLOPs of a launch: the stacked classes multiply their common window's zero padding too (ivln_gemm_desc.real_taps)
-    const double flops_of = 2.0 * d.M * (double)d.N * d.K * (KS == 2 && d.real_taps > 0 ? d.real_taps / 16.0 : 1.0);
     if (KS == 2) {
+        // (the stacked classes multiply their common window's zero padding too: ivln_gemm_desc.real_taps)
+        const double flops2 = flops * (d.real_taps > 0 ? d.real_taps / 16.0 : 1.0);
         if (d.stride != 1 || d.pad != 0 || d.Hout != d.Hin || d.Wout != d.Win || (d.M & 3) || d.grp_imgs > 0 || d.stat_partials || d.defer_epilogue ||
             d.splits > 1 || d.fuse_A_split || d.residual_after_relu || d.img_run_flags || d.K != d.Cin * 4 || d.HoWo != d.Hout * d.Wout ||
             d.N % d.HoWo != 0 || (d.Wout & 3) || d.Wout < 8 || (((uintptr_t)d.D | (uintptr_t)d.residual) & 15) || d.Ctot * 4 != d.M)
@@ -2390,10 +1919,7 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
         const int ov2 = d.tile_override;
         if (ov2 < 20) {  // few pixels: K split over the waves
             const int rc = bf3_ks_launch(d, s, nimg2, (ov2 == 10 || ov2 == 15) ? 1 : 0);
-            if (rc != IVLN_E_UNSUPPORTED || ov2 == 10 || ov2 == 15) {
-                if (rc == IVLN_OK) g_bf3_flops += flops_of, ++g_bf3_launches, ++g_bf3_kind[1];
-                return rc;
-            }
+            if (rc != IVLN_E_UNSUPPORTED || ov2 == 10 || ov2 == 15) return done(rc, flops2, 1, -1);
         }
         const int CUS2 = ivln_cu_count();
         auto blocks2 = [&](int cfg) {
@@ -2406,9 +1932,7 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
         if (ov2 >= 20 && ov2 < 20 + kBf3Cfgs) cfg2 = ov2 - 20;
         if (!force && blocks2(cfg2) < CUS2 / 2) return IVLN_E_UNSUPPORTED;
         d.splits = 1;
-        const int rc = launch_bf3_ks<2>(d, s, (const unsigned char*)d.A_split, d.a_split_grp_stride * 4, nimg2, cfg2, (d.Cin + CB - 1) / CB);
-        if (rc == IVLN_OK) g_bf3_flops += flops_of, ++g_bf3_launches, ++g_bf3_kind[0];
-        return rc;
+        return done(launch_bf3_ks<2>(d, s, (const unsigned char*)d.A_split, d.a_split_grp_stride * 4, nimg2, cfg2, (d.Cin + CB - 1) / CB), flops2, 0, -1);
     }
     // deep-K 1x1 convs: K split over the waves of a workgroup, fragments built in registers (k_conv1x1_bf3_ks);
     // IVLN_BF3_1X1_KS=0 | 1 = never | wherever eligible, tile_override 11 insists
@@ -2421,11 +1945,7 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     if (KS == 1 && ov < 20 && (ks1_env != 0 || ins1) && d.splits <= 1 && !d.defer_epilogue && d.HoWo == d.Hout * d.Wout &&
         d.K == d.Cin && d.N % d.HoWo == 0 && d.Hout == d.Hin && d.Wout == d.Win) {
         const int rc = bf3_1x1_ks_launch(d, s, (ks1_env == 1 || ins1) ? 1 : 0, ov == 12 ? 0 : (ov == 13 ? 1 : -1));
-        if (rc != IVLN_E_UNSUPPORTED || ins1) {
-            if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[ov == 13 ? 3 : (ov == 12 ? 2 : (d.Cin / CB <= 16 ? 3 : 2))];
-            if (rc == IVLN_OK && d.stat_tiles) *d.stat_tiles = 0;
-            return rc;
-        }
+        if (rc != IVLN_E_UNSUPPORTED || ins1) return done(rc, flops, ov == 13 ? 3 : (ov == 12 ? 2 : (d.Cin / CB <= 16 ? 3 : 2)), 0);
     }
     if (ins1 || (ins3 && KS != 3)) return IVLN_E_UNSUPPORTED;
     if (KS == 1) {  // 1x1, stride 1 or 2, no padding
@@ -2433,6 +1953,7 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
             return IVLN_E_UNSUPPORTED;
     } else if (KS == 3 && d.stride == 2) {  // stride-2 3x3 (pad 1, even input): the tiled kernel's phase-plane staging
         static const bool s2_off = getenv("IVLN_BF3_S2") && getenv("IVLN_BF3_S2")[0] == '0';  // A/B switch
+        // (Cin % CB: the stride-2 instantiations have no ragged-chunk test; launch_bf3_s2 checks it again)
         if ((s2_off && !force) || d.pad != 1 || d.Hin != 2 * d.Hout || d.Win != 2 * d.Wout || d.Cin % CB != 0 || d.fuse_A_split || d.stat_partials ||
             d.img_run_flags)
             return IVLN_E_UNSUPPORTED;
@@ -2455,25 +1976,18 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
         const unsigned char* a = (const unsigned char*)d.A_split;
         const int64_t gb = d.a_split_grp_stride * 4;
         // tiles: 64 or 128 channels x 128 pixels (4 x 32); 128 channels x 64 pixels (2 x 32, four waves of 32 channels) where the
-        // 128-pixel grid would leave CUs without a workgroup (layer 2 at 8 + 8 images: 128 workgroups); IVLN_BF3_FUSE_PX pins (tuning)
-        constexpr int px_env = 0;
+        // 128-pixel grid would leave CUs without a workgroup (layer 2 at 8 + 8 images: 128 workgroups)
         const int64_t wg128 = (int64_t)nimg * (d.Wout / 32) * (d.Hout / 4);
-        const bool px64 = d.M == 128 && d.Hout % 2 == 0 && (px_env ? px_env == 64 : wg128 < ivln_cu_count());
+        const bool px64 = d.M == 128 && d.Hout % 2 == 0 && wg128 < ivln_cu_count();
         const int rc = d.M == 64 ? launch_bf3_fused<1, 2, 2, 3>(d, s, a, gb, nimg)
                        : (px64 ? launch_bf3_fused<1, 4, 1, 3>(d, s, a, gb, nimg) : launch_bf3_fused<2, 2, 2, 3>(d, s, a, gb, nimg));
-        if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K + 2.0 * d.fuse_M * (double)d.N * d.M, ++g_bf3_launches, ++g_bf3_kind[0];
-        if (rc == IVLN_OK && d.stat_tiles) *d.stat_tiles = 0;
-        return rc;
+        return done(rc, flops + 2.0 * d.fuse_M * (double)d.N * d.M, 0, 0);
     }
     // pixel-starved deep 3x3 convs: K split over the waves of a workgroup, no slabs (k_conv_bf3_ks); IVLN_BF3_KS=0 | 1 = never | wherever eligible
     static const int ks_env = getenv("IVLN_BF3_KS") ? atoi(getenv("IVLN_BF3_KS")) : -1;
     if (KS == 3 && !s2 && ov < 20 && (ks_env != 0 || ins3) && d.splits <= 1) {
         const int rc = bf3_ks_launch(d, s, nimg, (ks_env == 1 || ins3) ? 1 : 0, ov == 14 ? 1 : (ov == 15 ? 2 : 0));
-        if (rc != IVLN_E_UNSUPPORTED || ins3) {
-            if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[1];
-            if (rc == IVLN_OK && d.stat_tiles) *d.stat_tiles = 0;
-            return rc;
-        }
+        if (rc != IVLN_E_UNSUPPORTED || ins3) return done(rc, flops, 1, 0);
     }
     const int nch = ((d.Cin + CB - 1) / CB + bf3_stage_chunks(KS) - 1) / bf3_stage_chunks(KS);  // stages: what blockIdx.z can split
     auto tiles_of = [&](int cfg) {
@@ -2487,8 +2001,6 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
         const int64_t round = (int64_t)CUS * slots, rounds = (nb + round - 1) / round;
         return nb * 4 >= rounds * round * 3;
     };
-    constexpr int cfg_env = -1;  // tuning
-    constexpr int split_env = 0;
     // the widest tile that fills the chip on its own; else the 4-wave tiles (two or three workgroups per CU) with the channel
     // chunks split over blockIdx.z (raw slabs reduced by k_splitk_epilogue, like the fp32 kernels)
     int cfg = -1, splits = 1;
@@ -2496,19 +2008,17 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     // (4-wave tiles, measured on RedNet's 3x3 shapes at 8 + 8 stacked images against the fp32 kernels: 128 x 128 wins from
     //  2 M outputs - 57 vs 64 us on 128 x 16384, 50 vs 67 on 256 x 4096 and 512 x 1024 -, 64 x 128 below - 41 vs 46 on
     //  128 x 8192, 37.5 vs 44 on 256 x 2048 and 512 x 512; 64-channel convs that need them lose - 42 vs 38 us on 64 x 32768)
-    constexpr bool nosplit4 = true;  // A/B: =0 restores the split 64 x 128 tiles
-    constexpr int cfg32_env = -1;  // tuning: 0 | 6
-    if (d.M <= 32) cfg = cfg32_env >= 0 ? cfg32_env : 6;
+    //  (the 64 x 128 tile that gives every CU a workgroup stays unsplit)
+    if (d.M <= 32) cfg = 6;
     else if (d.M <= 64)
         cfg = (big_ok && KS != 1 && fills(blocks_of(1), 1)) ? 1
-              : (fills(blocks_of(2), 1) ? 2 : ((force || (nosplit4 && blocks_of(4) >= CUS)) ? 4 : -1));
+              : (fills(blocks_of(2), 1) ? 2 : ((force || blocks_of(4) >= CUS) ? 4 : -1));
     // (64 x 32768, the decoder's 64-channel convs at 64 x 64: the 64 x 128 tile UNSPLIT - one workgroup per CU - 24.9 us against the
     //  fp32 kernel's 37.2 and 35.8 with its channel chunks split three ways + the reduction launch: tools/conv_cfg_sweep.py)
     // (round 5, aligned-group staging: the 64 x 128 tile now beats 128 x 128 wherever the latter leaves CUs without a workgroup -
     //  128 x 16384: 42.7 vs 50.9 us, 256 x 4096: 43.2 vs 45.3)
     else cfg = fills(blocks_of(3), 1) ? 3 : (fills(blocks_of(2), 1) ? 2 : (((int64_t)d.M * d.N >= (1 << 21) && blocks_of(5) >= CUS) ? 5 : 4));
     if (cfg < 0) return IVLN_E_UNSUPPORTED;
-    if (cfg_env >= 0 && cfg_env < kBf3Cfgs && !(cfg_env == 0 && d.M > 32)) cfg = cfg_env;
     if (d.tile_override >= 20 && d.tile_override < 20 + kBf3Cfgs) cfg = d.tile_override - 20;  // (tuning: tools/conv_cfg_sweep.py pins a tile)
     if ((cfg == 0 && !big_ok) || (KS == 1 && (cfg <= 1 || cfg == 6))) return IVLN_E_UNSUPPORTED;
     const int64_t nb = blocks_of(cfg);
@@ -2520,18 +2030,12 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     if (cfg >= 4) {
         const int slots = cfg == 4 ? 3 : 2;
         const bool may_split = d.splits == 0 && d.ws && nch >= 2 && !d.stat_partials;
-        if (may_split && nb < (int64_t)CUS * slots && !(cfg == 4 && nosplit4 && nb >= CUS)) {  // (128 x 16384: 45.0 unsplit, 53.0 split two ways)
+        if (may_split && nb < (int64_t)CUS * slots && !(cfg == 4 && nb >= CUS)) {  // (128 x 16384: 45.0 unsplit, 53.0 split two ways)
             const int64_t want = (int64_t)CUS * slots;
             splits = (int)((want + nb - 1) / nb);
             if (splits > nch) splits = nch;
             if (splits > 16) splits = 16;
             const int64_t cap = d.ws_floats / ((int64_t)d.M * d.N);
-            if (splits > cap) splits = (int)cap;
-            if (splits < 1) splits = 1;
-        }
-        if (split_env > 0 && may_split) {
-            splits = split_env > nch ? nch : split_env;
-            const int64_t cap = d.ws_floats / ((int64_t)d.M * d.N);  // (the slabs have to fit the workspace whatever the tuning knob says)
             if (splits > cap) splits = (int)cap;
             if (splits < 1) splits = 1;
         }
@@ -2552,15 +2056,12 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
                    : s2      ? launch_bf3_s2(d, s, (const unsigned char*)d.A_split, gb, nimg, cfg, cps)
                    : KS == 3 ? launch_bf3_ks<3>(d, s, (const unsigned char*)d.A_split, gb, nimg, cfg, cps)
                              : launch_bf3_ks<1>(d, s, (const unsigned char*)d.A_split, gb, nimg, cfg, cps);
-    if (rc == IVLN_OK) g_bf3_flops += 2.0 * d.M * (double)d.N * d.K, ++g_bf3_launches, ++g_bf3_kind[0];
-    if (rc == IVLN_OK && d.stat_tiles) *d.stat_tiles = d.stat_partials ? (int)(tiles * (BN / 128)) : 0;
-    return rc;
+    return done(rc, flops, 0, d.stat_partials ? (int)(tiles * (BN / 128)) : 0);
 }
 
 // The 7x7 weight gradient on the split-bf16 arithmetic (k_wgrad_bf3).  IVLN_E_UNSUPPORTED -> the fp32 MFMA weight-gradient kernel.
 int ivln_wgrad_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
-    constexpr bool disabled = false;  // A/B switches
-    if ((!d.split_ok && !force) || (disabled && !force)) return IVLN_E_UNSUPPORTED;
+    if (!d.split_ok && !force) return IVLN_E_UNSUPPORTED;
     if (d.amode != AMODE_NCHW_P || d.bmode != BMODE_IM2COL_T || d.dmode != DMODE_DENSE || d.stride != 1 || d.dil != 1 || d.Cin <= 0 ||
         d.N != d.Cin * 49 || d.defer_epilogue || d.pad != 3)
         return IVLN_E_UNSUPPORTED;
@@ -2574,8 +2075,7 @@ int ivln_wgrad_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     // tile: 32 x 512, 64 x 512 or 128 x 256 (channels x columns); strips over blockIdx.z until a workgroup per CU
     // (32-channel outputs: 14 x 49 = 686 columns are two tiles of 384 - six waves - with 11 % of the columns idle; two tiles of
     //  512 left 33 % idle)
-    constexpr int l1_env = 0;  // tuning: 6 | 8
-    const bool six = d.M <= 32 && (l1_env ? l1_env == 6 : (d.N + 383) / 384 * 384 < (d.N + 511) / 512 * 512);
+    const bool six = d.M <= 32 && (d.N + 383) / 384 * 384 < (d.N + 511) / 512 * 512;
     // x promised exact in bf16 (split_ok = 2): the one-piece form, as 32 x 256 tiles of four waves - 43 KB of LDS, 3 workgroups per CU
     // (9.09 against 9.02 ms per update with 32 x 384 tiles of six waves, two per CU; 9.44 with the three-piece form)
     const bool xe = d.split_ok == 2 && d.M <= 32 && d.Wout == 64;
@@ -2585,10 +2085,9 @@ int ivln_wgrad_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     int splits = 1;
     if (d.splits == 0) {
         if (d.ws) {
-            constexpr int want_env = 0;  // tuning
             // one workgroup per CU (LDS): as many splits as keep the grid inside whole rounds of 256 (13 column tiles x 20
             // splits = 260 workgroups ran a second round for four of them)
-            const int64_t want = want_env > 0 ? want_env : (xe ? 3 : 1) * (int64_t)ivln_cu_count();
+            const int64_t want = (xe ? 3 : 1) * (int64_t)ivln_cu_count();
             splits = (int)(want / blocks);
             if (splits < 1) splits = 1;
             if (splits > strips) splits = strips;

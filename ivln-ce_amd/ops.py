@@ -393,7 +393,7 @@ class Deferred:
 
 # 3x3 / 7x7 convs with both operands as three bf16 pieces each on the bf16 MFMA pipe (csrc/conv_bf3.hip): exact pieces, six
 # of the nine piece products, fp32 accumulation - as close to the exact conv as the fp32 MFMA kernels.
-# IVLN_SPLIT_BF16=0 keeps the fp32 MFMA kernels everywhere (A/B); the C side has IVLN_NO_SPLIT_BF16 for the same.
+# IVLN_SPLIT_BF16=0 keeps the fp32 MFMA kernels everywhere (A/B): A_split is then not passed, the C side has no switch of its own.
 SPLIT_BF16 = os.environ.get("IVLN_SPLIT_BF16", "1") != "0"
 # the 7x7 weight gradients on the same arithmetic (k_wgrad_bf3; 1.1-1.7x the fp32 MFMA weight-gradient kernel at the update's shapes)
 SPLIT_BF16_WGRAD = os.environ.get("IVLN_SPLIT_BF16_WGRAD", "1") != "0"
