@@ -44,6 +44,7 @@ def build_all(force=False, verbose=True):
     objs = []
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))]
     headers.append(os.path.join(HERE, "..", "include", "ivln_hip.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_rednet_glue.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

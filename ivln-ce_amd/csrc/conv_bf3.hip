@@ -1200,6 +1200,13 @@ int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin =
     // (32 chunks over MANY pixels - 256 x 16384 x 512, layer 3's first reduction at 8 + 8 images - would be four rounds of one
     //  K-split workgroup per CU: the wave tiles take it, 43.6 against 51.5 us on the tiled 1x1 form and 52.1 K-split, tools/conv_cfg_sweep.py)
     if (nch == 32 && (int64_t)((d.N + 127) / 128) * ((d.M + 31) / 32) > 2 * (int64_t)ivln_cu_count()) wt = true;
+    // (24 and 48 chunks over MANY pixels - 512 x 16384 x 384 and 1024 x 4096 x 768, the stride-2 entry blocks' expansion with the
+    //  downsample branch in its K at 8 + 8 images (rednet.py: MERGE_ENTRY_CONV3) - are the same case.  Both forms pinned, image-
+    //  grouped, shift + ReLU, back to back in one call: 47.6 us as wave tiles against 76.6 K-split (2048 workgroups) for the
+    //  first, 47.0 against 69.3 (1024 workgroups) for the second; the downsample conv + conv3-with-residual pairs they replace
+    //  took 61.4 and 52.8.  2048 x 1024 x 1536 - 96 chunks, beyond the wave-tile form, whose 128 workgroups would leave half
+    //  of the CUs empty anyway - is 512 K-split workgroups, which the rule below already takes: 52.2 us against the pair's 65.1.)
+    if ((nch == 24 || nch == 48) && (int64_t)((d.N + 127) / 128) * ((d.M + 31) / 32) > 2 * (int64_t)ivln_cu_count()) wt = true;
     if (form_pin >= 0) wt = form_pin == 1;
     if (wt && nch > 64) wt = false;
     if (wt && d.accumulate) return IVLN_E_UNSUPPORTED;  // (the wave-tile epilogue is straight-line code: no D += form)

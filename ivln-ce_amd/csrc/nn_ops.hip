@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/ivln_hip.h"
+#include "../../include/ivln_rednet_glue.h"
 
 namespace {
 
@@ -500,6 +501,39 @@ __global__ __launch_bounds__(256) void k_subsample2_x4(const float* __restrict__
     const float4* r = reinterpret_cast<const float4*>(x + (nc * H + 2 * ho) * W + 8 * j);
     const float4 a = r[0], b = r[1];
     *reinterpret_cast<float4*>(y + (nc * Ho + ho) * Wo + 4 * j) = make_float4(a.x, a.z, b.x, b.z);
+}
+
+// The fusion add at the end of a RedNet encoder layer and the gather above for the next layer's stride-2 entry block in ONE pass
+// (rednet.py:199-222; include/ivln_rednet_glue.h): a thread owns eight consecutive floats of a row of the RGB half of the
+// stacked (2 B, C, H, W) batch - two 16-byte loads from each half, a += b (k_add's one fp32 add), two 16-byte stores back - and,
+// on even rows, sends every second value of the sum and of the depth half to their images' channel slice of dst as one
+// 16-byte store each.  k_subsample2_x4 re-read what k_add had just written: 1.5 x the stacked tensor's bytes less.
+// !ADD: the gather alone of a (B, C, H, W) tensor into the slice (the encoders as separate chains), x is only read.
+template <bool ADD>
+__global__ __launch_bounds__(256) void k_add_subsample2_x4(float* __restrict__ x, float* __restrict__ dst, int64_t total8, int B, int C,
+                                                          int H, int W, int ctot, int coff) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total8) return;
+    const int W8 = W >> 3, Ho = H >> 1, Wo = W >> 1;
+    const int j = (int)(idx % W8);
+    const int h = (int)((idx / W8) % H);
+    if (!ADD && (h & 1)) return;
+    const int64_t nc = idx / ((int64_t)W8 * H);  // (image, channel) of the first B images
+    float4* const pa = reinterpret_cast<float4*>(x + (nc * H + h) * W + 8 * j);
+    float4 a0 = pa[0], a1 = pa[1];
+    float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+    if (ADD) {
+        const float4* const pb = reinterpret_cast<const float4*>(x + (int64_t)B * C * H * W + (nc * H + h) * W + 8 * j);
+        b0 = pb[0], b1 = pb[1];
+        a0.x += b0.x, a0.y += b0.y, a0.z += b0.z, a0.w += b0.w;
+        a1.x += b1.x, a1.y += b1.y, a1.z += b1.z, a1.w += b1.w;
+        pa[0] = a0, pa[1] = a1;
+        if (h & 1) return;
+    }
+    const int n = (int)(nc / C), c = (int)(nc - (int64_t)n * C);
+    const int64_t o = (((int64_t)n * ctot + coff + c) * Ho + (h >> 1)) * Wo + 4 * j;
+    *reinterpret_cast<float4*>(dst + o) = make_float4(a0.x, a0.z, a1.x, a1.z);
+    if (ADD) *reinterpret_cast<float4*>(dst + o + (int64_t)B * ctot * Ho * Wo) = make_float4(b0.x, b0.z, b1.x, b1.z);
 }
 
 // MaxPool2d(3, 2, 1) (RedNet's stem, rednet.py:195-197), four consecutive outputs of a row per thread: their windows cover input
@@ -1581,6 +1615,20 @@ int ivln_add_f32(const float* a, const float* b, float* y, int64_t n, int relu, 
     return LAUNCH_OK();
 }
 
+int ivln_add_subsample2_f32(float* x, int B, int C, int H, int W, int add, float* dst, int dst_ctot, int dst_coff, void* stream) {
+    if (!x || !dst || B <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 7) || dst_coff < 0 || dst_coff + C > dst_ctot ||
+        ((((uintptr_t)x) | ((uintptr_t)dst)) & 15))
+        return IVLN_E_INVALID;
+    const int64_t total8 = (int64_t)B * C * H * (W / 8);
+    if (add)
+        hipLaunchKernelGGL(k_add_subsample2_x4<true>, dim3(nblk(total8)), dim3(256), 0, (hipStream_t)stream, x, dst, total8, B, C, H, W,
+                           dst_ctot, dst_coff);
+    else
+        hipLaunchKernelGGL(k_add_subsample2_x4<false>, dim3(nblk(total8)), dim3(256), 0, (hipStream_t)stream, x, dst, total8, B, C, H, W,
+                           dst_ctot, dst_coff);
+    return LAUNCH_OK();
+}
+
 int ivln_copy2d_f32(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int rows, int cols,
                     int broadcast_rows, void* stream) {
     hipLaunchKernelGGL(k_copy2d, dim3(nblk((int64_t)rows * cols)), dim3(256), 0, (hipStream_t)stream, src, ld_src,
@@ -1643,6 +1691,10 @@ int ivln_rednet_fwd(const ivln_rednet_op* table, int n_ops, const uint8_t* rgb, 
                 if (dst) rc = ivln_argmax_channels_u8((const float*)op.src0, op.i[0], op.i[1], op.i[2], dst, stream);
                 break;
             }
+            case IVLN_OP_ADD_SUBSAMPLE2:
+                rc = ivln_add_subsample2_f32((float*)op.src0, op.i[0], op.i[1], op.i[2], op.i[3], op.i[6], (float*)op.dst, op.i[4], op.i[5],
+                                             stream);
+                break;
             default:
                 break;
         }

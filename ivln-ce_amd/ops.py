@@ -57,7 +57,7 @@ class RednetOp(C.Structure):
                 ("gemm", GemmDesc)]
 
 
-OP_GEMM, OP_ADD, OP_POOL, OP_RGB_NORM, OP_AFFINE, OP_ARGMAX_U8 = range(6)
+OP_GEMM, OP_ADD, OP_POOL, OP_RGB_NORM, OP_AFFINE, OP_ARGMAX_U8, OP_ADD_SUBSAMPLE2 = range(7)  # (the last: include/ivln_rednet_glue.h)
 
 
 class OpRecorder:
@@ -139,6 +139,7 @@ def _L():
         L.ivln_rgb_resize_normalize_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
         L.ivln_affine_f32.argtypes = [vp, vp, i64, f32, f32, vp]
         L.ivln_add_f32.argtypes = [vp, vp, vp, i64, i32, vp]
+        L.ivln_add_subsample2_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp]
         L.ivln_copy2d_f32.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp]
         L.ivln_tour_memory_f32.argtypes = [vp, i64, vp, i64, vp, i32, i32, vp, i64, vp, i64, vp]
         # recurrent state encoders (csrc/state_rnn.hip)
@@ -1649,6 +1650,21 @@ def add(a, b, relu=False, out=None):
     if _REC is not None:
         _rec(OP_ADD, (int(bool(relu)),), n=a.numel(), src0=a.data_ptr(), src1=b.data_ptr(), dst=out.data_ptr())
     return out
+
+
+def add_subsample2(x, B, dst, coff=0, add=True):
+    """The fusion add at the end of a RedNet encoder layer + the stride-2 gather in front of the next layer's entry block as one
+    launch (include/ivln_rednet_glue.h): x (2 B, C, H, W) stacked [RGB ; depth], x[:B] += x[B:] in place, and x[:, :, ::2, ::2]
+    of the result lands in dst[:, coff : coff + C] (dst (2 B, Ctot, H / 2, W / 2), contiguous).  add=False: x is (B, C, H, W),
+    the gather alone.  Returns x[:B] (the fused tensor) | x."""
+    N, Cc, H, W = x.shape
+    if N != (2 * B if add else B) or tuple(dst.shape) != (N, dst.shape[1], H // 2, W // 2) or H % 2 or W % 8:
+        raise _lib.IvlnError(f"add_subsample2: x {tuple(x.shape)}, dst {tuple(dst.shape)}, B {B}")
+    check(_L().ivln_add_subsample2_f32(dptr(x), B, Cc, H, W, int(bool(add)), dptr(dst), dst.shape[1], coff, stream_ptr()),
+          "ivln_add_subsample2_f32")
+    if _REC is not None:
+        _rec(OP_ADD_SUBSAMPLE2, (B, Cc, H, W, dst.shape[1], coff, int(bool(add))), src0=x.data_ptr(), dst=dst.data_ptr())
+    return x[:B] if add else x
 
 
 def copy_multi(pairs):

@@ -17,6 +17,14 @@ from . import ops
 
 # RGB + depth encoders as one image-grouped pass (A/B switch: IVLN_REDNET_NO_GROUP=1 runs them as two chains)
 GROUP_ENCODERS = True  # (False: the two encoders as separate launch chains - what tests compare the stacked form with)
+# The stride-2 entry blocks of layers 2-4: relu(s3 (W3 y2) + b3 + sd (Wd x_sub) + bd) as ONE 1x1 conv over the channel
+# concatenation [x_sub ; y2] with the weights [diag(sd) Wd | diag(s3) W3] and the shift b3 + bd - the downsample branch's
+# output is never written or read back, one launch less per block.  (False: downsample conv, then conv3 with its residual -
+# what tests compare the merged form with)
+MERGE_ENTRY_CONV3 = True
+# ... and the fusion add in front of such a block emits the block's gathered input (every second pixel of every second row of
+# the stacked batch) in the same pass, straight into the concatenation buffer.  (False: add, then a gather launch)
+FUSE_ADD_GATHER = True
 
 
 def _conv3x3(cin, cout, stride=1):
@@ -47,6 +55,25 @@ class _Folded:
             (sa, ba), (sb, bb) = self.bn(bn_a), self.bn(bn_b)
             w = torch.stack([conv_a.weight.detach(), conv_b.weight.detach()]).contiguous()
             self.c[k] = (w, torch.cat([sa, sb]).contiguous(), torch.cat([ba, bb]).contiguous())
+        return self.c[k]
+
+    def merged3(self, blk, blk_d=None):
+        """A stride-2 entry block's downsample conv and conv3 as one 1x1 conv over [x_sub ; y2] (MERGE_ENTRY_CONV3): weights
+        (Cout, Cin + Cmid, 1, 1) = [diag(sd) Wd | diag(s3) W3] with both folded BatchNorm scales inside, shift b3 + bd;
+        with `blk_d` the RGB and the depth encoder's stacked (2, Cout, Cin + Cmid, 1, 1) / (2 Cout) like pair().  Folded once
+        (frozen network) into persistent tensors: ops.packed_conv_weights caches their split image."""
+        k = ("m3", id(blk.conv3), blk_d is not None)
+        if k not in self.c:
+            def one(b):
+                (sd, bd), (s3, b3) = self.bn(b.downsample[1]), self.bn(b.bn3)
+                wd, w3 = b.downsample[0].weight.detach(), b.conv3.weight.detach()
+                return torch.cat([wd * sd.view(-1, 1, 1, 1), w3 * s3.view(-1, 1, 1, 1)], dim=1), b3 + bd
+            if blk_d is None:
+                w, sh = one(blk)
+                self.c[k] = (w.contiguous(), sh)
+            else:
+                (wa, sa), (wb, sb) = one(blk), one(blk_d)
+                self.c[k] = (torch.stack([wa, wb]).contiguous(), torch.cat([sa, sb]).contiguous())
         return self.c[k]
 
     def classes(self, convt: nn.ConvTranspose2d):
@@ -105,6 +132,10 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
     def forward_hip(self, x, f: _Folded):
+        if _entry_merge_ok(self, x, 1):
+            buf = _entry_buf(self, x)
+            ops.add_subsample2(x, x.shape[0], buf, add=False)
+            return _entry_merged(self, None, x, buf, f)
         residual = x
         if self.downsample is not None:
             s, b = f.bn(self.downsample[1])
@@ -138,9 +169,45 @@ def _conv_pair(x2, w2, s2, b2, stride=1, pad=0, residual=None, relu=False):
     return out
 
 
-def _bottleneck_pair(blk: Bottleneck, blk_d: Bottleneck, x2, f: _Folded):
+def _entry_merge_ok(blk: Bottleneck, x, G):
+    """MERGE_ENTRY_CONV3 takes this block at this input: a stride-2 block with a 1x1 downsample branch, a map the gather's
+    16-byte accesses fit, and - stacked encoders - pixel tiles of the 1x1 kernels that do not straddle the weight sets."""
+    # (ops.S2_GATHER off: the downsample conv reads its input strided - there is no gathered tensor to concatenate)
+    if not MERGE_ENTRY_CONV3 or not ops.S2_GATHER or blk.stride != 2 or blk.downsample is None or not x.is_contiguous():
+        return False
+    N, _, H, W = x.shape
+    return H % 2 == 0 and W % 8 == 0 and (G == 1 or (N % G == 0 and (N // G * (H // 2) * (W // 2)) % 128 == 0))
+
+
+def _entry_buf(blk: Bottleneck, x):
+    """[x_sub ; y2]: the gathered input in channels [0, Cin), conv2's output behind it."""
+    N, Cin, H, W = x.shape
+    return torch.empty((N, Cin + blk.conv2.out_channels, H // 2, W // 2), dtype=torch.float32, device=x.device)
+
+
+def _entry_merged(blk: Bottleneck, blk_d, x, buf, f: _Folded):
+    """The entry block with buf[:, :Cin] already holding x[:, :, ::2, ::2]: conv1, conv2 into buf[:, Cin:], the merged conv3."""
+    Cin, Ctot = x.shape[1], buf.shape[1]
+    if blk_d is None:
+        w1, (s1, b1), w2, (s2, b2) = blk.conv1.weight, f.bn(blk.bn1), blk.conv2.weight, f.bn(blk.bn2)
+    else:
+        w1, s1, b1 = f.pair(blk.conv1, blk.bn1, blk_d.conv1, blk_d.bn1)
+        w2, s2, b2 = f.pair(blk.conv2, blk.bn2, blk_d.conv2, blk_d.bn2)
+    y = ops.conv2d(x, w1, scale=s1, shift=b1, relu=True)
+    ops.conv2d(y, w2, stride=2, pad=1, scale=s2, shift=b2, relu=True, out=buf[:, Cin:], out_ctot=Ctot)
+    wm, shm = f.merged3(blk, blk_d)
+    return ops.conv2d(buf, wm, shift=shm, relu=True)
+
+
+def _bottleneck_pair(blk: Bottleneck, blk_d: Bottleneck, x2, f: _Folded, entry_buf=None):
     """The same bottleneck of the RGB encoder (first half of the stacked batch) and of the depth encoder (second
-    half) in one pass: 3-4 launches instead of 6-8, every launch with twice the output tiles."""
+    half) in one pass: 3-4 launches instead of 6-8, every launch with twice the output tiles.
+    entry_buf: the concatenation buffer of a merged entry block whose gathered input the fusion add has already written."""
+    if entry_buf is not None or _entry_merge_ok(blk, x2, 2):
+        if entry_buf is None:
+            entry_buf = _entry_buf(blk, x2)
+            ops.add_subsample2(x2, x2.shape[0], entry_buf, add=False)
+        return _entry_merged(blk, blk_d, x2, entry_buf, f)
     residual = x2
     if blk.downsample is not None:
         w, s, b = f.pair(blk.downsample[0], blk.downsample[1], blk_d.downsample[0], blk_d.downsample[1])
@@ -314,11 +381,20 @@ class RedNet(nn.Module):
             P = ops.pool2d(S, 3, 2, 1, "max")
             fuses = []
             _stage_done("stem")
-            for li, (la, lb) in enumerate(((self.layer1, self.layer1_d), (self.layer2, self.layer2_d),
-                                           (self.layer3, self.layer3_d), (self.layer4, self.layer4_d))):
-                for blk, blk_d in zip(la, lb):
-                    P = _bottleneck_pair(blk, blk_d, P, f)
-                fuses.append(ops.add(P[:B], P[B:], out=P[:B]))
+            layers = ((self.layer1, self.layer1_d), (self.layer2, self.layer2_d), (self.layer3, self.layer3_d),
+                      (self.layer4, self.layer4_d))
+            buf = None
+            for li, (la, lb) in enumerate(layers):
+                for bi, (blk, blk_d) in enumerate(zip(la, lb)):
+                    P = _bottleneck_pair(blk, blk_d, P, f, entry_buf=buf if bi == 0 else None)
+                # the fusion add; in front of a merged entry block it also writes that block's gathered input
+                nxt = layers[li + 1][0][0] if li + 1 < len(layers) else None
+                if FUSE_ADD_GATHER and nxt is not None and _entry_merge_ok(nxt, P, 2):
+                    buf = _entry_buf(nxt, P)
+                    fuses.append(ops.add_subsample2(P, B, buf))
+                else:
+                    buf = None
+                    fuses.append(ops.add(P[:B], P[B:], out=P[:B]))
                 _stage_done(f"layer{li + 1}")
             fuse1, fuse2, fuse3, fuse4 = fuses
         else:
