@@ -314,7 +314,8 @@ int ivln_conv_pack_weights_f32(const float* W, int M, int Cin, int KS, float* ou
  * conv -> GroupNorm -> ReLU -> conv ..., Bottleneck tails relu(GN(c3) + GN_ds(ds)) / relu(GN(c3) + identity) feeding
  * the next block's conv1 (A) and downsample conv (B).  act_out (N, C, H', W') receives the activation when a later
  * block needs it as its identity.  IVLN_E_UNSUPPORTED: (C/groups)*H*W > 8192, odd C/groups, k not in {1, 3}, tiles +
- * weights that do not fit 152 KB of LDS. */
+ * weights that do not fit 152 KB of LDS.  Every shape inside that envelope is computed correctly, whatever the number
+ * of 32 x 32 output tiles a workgroup ends up with (channel counts and maps need not be powers of two). */
 typedef struct ivln_gn_conv_desc {
     const float* x;       /* slabs of [C][N*H*W] */
     int splits;
@@ -414,7 +415,8 @@ int ivln_host_device_ptr(void* host, void** dev);
  * per producing workgroup; the consumer merges them in part order (Chan), i.e. the variance is the two-pass one.
  * act_out (N, C, H, W) optionally receives `in` (a later block's identity).  habitat-lab ResNetEncoder Bottleneck,
  * models/encoders/resnet_encoders.py:31-43, 95.  IVLN_E_UNSUPPORTED: W > 32*k ... see gn_conv.hip (strip + weights
- * + output tile must fit 152 KB of LDS, C and Cout multiples of 2 * groups). */
+ * + output tile must fit 152 KB of LDS, C and Cout multiples of 2 * groups).  Every shape inside that envelope is
+ * computed correctly, whatever the number of 32 x 32 output tiles a workgroup ends up with. */
 typedef struct ivln_nconv_desc {
     const float* x;        /* raw (pre-GroupNorm) input [C][N][H][W] - the one-slab layout of the deferred ivln_gemm_f32 /
                               ivln_gn_conv_f32 outputs - or, when stats == NULL, the activated input (N, C, H, W) */

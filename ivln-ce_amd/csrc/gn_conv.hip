@@ -240,7 +240,8 @@ __device__ __forceinline__ int padded_row(int Kb) { return ((Kb + 3) & ~3) + 4; 
 // v_mfma_f32_32x32x2_f32 (the two k slots = a channel pair), one tile per wave.  A operand: the staged weight slice
 // wl[row][Kbp] (LDS), B operand: the tile gathered through per-lane tap addresses (zero padding and pixels past the
 // map read the block's zero word with channel stride 0 - no conditional load).  When a block has fewer than 8 tiles
-// its waves split the channel pairs of a tile between them and the partial tiles are summed through LDS (`part`).
+// its waves split the channel pairs of a tile between them and the partial tiles are summed through LDS (`part`, 8
+// partial tiles: tiles x waves per tile never exceeds 8).
 template <int KSZ>
 __device__ __forceinline__ void partial_conv(const float* act, int cpg, int H, int W, const float* __restrict__ w, int C,
                                              int c0, int co_beg, int co_end, int stride, int pad, int Ho, int Wo,
@@ -269,6 +270,7 @@ __device__ __forceinline__ void partial_conv(const float* act, int cpg, int H, i
         const int T = ((nrow + 31) >> 5) * ptl;
         int ksl = (T >= 8 || !part) ? 0 : (T >= 4 ? 1 : (T >= 2 ? 2 : 3));  // log2 of the waves per tile
         while ((1 << ksl) > hc) --ksl;
+        while (ksl > 0 && (T << ksl) > 8) --ksl;  // `part` holds 8 partial tiles: T = 3 shares by 2, T = 5..7 not at all
         const int KS = 1 << ksl;
         for (int item = wave; item < T * KS; item += NW) {
             const int tile = item >> ksl, ks = item - (tile << ksl);
