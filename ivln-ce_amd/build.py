@@ -27,6 +27,7 @@ SOURCES = {
     "instr_rnn.hip": [],
     "nn_ops.hip": [],
     "train_ops.hip": [],
+    "depth_bwd.hip": [],
     "dtw.cpp": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -45,6 +46,7 @@ def build_all(force=False, verbose=True):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))]
     headers.append(os.path.join(HERE, "..", "include", "ivln_hip.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_rednet_glue.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_depth_bwd.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

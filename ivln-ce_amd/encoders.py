@@ -351,6 +351,36 @@ class _Bottleneck(nn.Module):
         y = ops.groupnorm(y, c[4].weight, c[4].bias, c[4].num_groups, c[4].eps, relu=True)
         return ops.conv2d(y, c[6].weight, defer=True), ds
 
+    def forward_train(self, x, save):
+        """The block with every conv output materialised and every GroupNorm's statistics kept: what
+        train.depth_encoder_backward walks.  Appends dict(x, l1, l2, l3, ds | None, out) to `save`; l* / ds =
+        dict(raw, mean, rstd[, out]) of one conv -> GroupNorm (-> ReLU) layer."""
+        c = self.convs
+        r1 = ops.conv2d(x, c[0].weight)
+        l1 = _gn_train(r1, c[1], relu=True)
+        r2 = ops.conv2d(l1["out"], c[3].weight, stride=self.stride, pad=1)
+        l2 = _gn_train(r2, c[4], relu=True)
+        r3 = ops.conv2d(l2["out"], c[6].weight)
+        ds, identity = None, x
+        if self.downsample is not None:
+            rd = ops.conv2d(x, self.downsample[0].weight, stride=self.stride)
+            ds = _gn_train(rd, self.downsample[1], relu=False)
+            identity = ds.pop("out")  # (only the tail reads it)
+        l3 = _gn_train(r3, c[7], relu=True, residual=identity)
+        out = l3.pop("out")
+        save.append(dict(x=x, l1=l1, l2=l2, l3=l3, ds=ds, out=out))
+        return out
+
+
+def _gn_train(raw, gn, relu, residual=None):
+    """GroupNorm (+ residual) (+ ReLU) of a materialised conv output with the statistics saved -> dict(raw, mean, rstd, out)."""
+    n = raw.shape[0] * gn.num_groups
+    mean = torch.empty(n, dtype=torch.float32, device=raw.device)
+    rstd = torch.empty(n, dtype=torch.float32, device=raw.device)
+    out = ops.groupnorm(raw, gn.weight, gn.bias, gn.num_groups, gn.eps, relu=relu, residual=residual, save_mean=mean,
+                        save_rstd=rstd)
+    return dict(raw=raw, mean=mean, rstd=rstd, out=out)
+
 
 class _ResNet50GN(nn.Module):
     def __init__(self, in_channels, base_planes, ngroups):
@@ -497,6 +527,20 @@ class _ResNet50GN(nn.Module):
                 y = blk.forward_hip(y)
         return y
 
+    def forward_train(self, x, save):
+        """forward_hip with materialised conv outputs and saved statistics (a trainable encoder's update pass):
+        save["stem"] = dict(x, raw, mean, rstd, out = the activation in front of the max-pool), save["blocks"] = one
+        entry per bottleneck (_Bottleneck.forward_train)."""
+        c, gn = self.conv1[0], self.conv1[1]
+        stem = _gn_train(ops.conv2d(x, c.weight, stride=2, pad=3), gn, relu=True)
+        stem["x"] = x
+        save["stem"], save["blocks"] = stem, []
+        y = ops.pool2d(stem["out"], 3, 2, 1, "max")
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                y = blk.forward_train(y, save["blocks"])
+        return y
+
 
 class ResNetEncoder(nn.Module):
     """habitat-lab ResNetEncoder for a depth-only observation space: avg_pool2d(2) -> GN-ResNet50 ->
@@ -525,9 +569,41 @@ class ResNetEncoder(nn.Module):
     def is_blind(self):
         return self._n_input_depth == 0
 
-    def forward(self, observations, out=None, out_ctot=0):
+    @property
+    def trains(self):
+        """A parameter of the encoder takes a gradient (MODEL.DEPTH_ENCODER.trainable, resnet_encoders.py:31-43)."""
+        return any(p.requires_grad for p in self.parameters())
+
+    def forward_train(self, observations, save, out=None, out_ctot=0):
+        """The update pass of a trainable encoder: the same network as `forward`, layer by layer with materialised conv
+        outputs, and in `save` (a dict) per layer the conv input, the raw GroupNorm input, its mean / rstd and the activated
+        output - what train.depth_encoder_backward reads.  Callers take it only for a pass that will be differentiated
+        (the policy's training forward with a `save` dict, which runs under the autograd Function's no_grad) and only when
+        `trains`; every other call keeps the chain, pair and persistent paths of `forward`."""
+        depth = observations["depth"].to(torch.float32).contiguous()
+        B, H, W, Cd = depth.shape
+        assert Cd == 1, "depth-only encoder"
+        c, gn = self.compression[0], self.compression[1]
+        hw = self.output_shape[1] * self.output_shape[2]
+        x = ops.pool2d(depth.view(B, 1, H, W), 2, 2, 0, "avg")  # F.avg_pool2d(x, 2)
+        y = self.backbone.forward_train(x, save)
+        raw = ops.conv2d(y, c.weight, pad=1)
+        mean = torch.empty(B * gn.num_groups, dtype=torch.float32, device=depth.device)
+        rstd = torch.empty(B * gn.num_groups, dtype=torch.float32, device=depth.device)
+        # (the backward masks with a dense copy of the output: `out` may be a channel slice of the policy's buffer)
+        feats = ops.groupnorm(raw, gn.weight, gn.bias, gn.num_groups, gn.eps, relu=True, save_mean=mean, save_rstd=rstd)
+        save["comp"] = dict(x=y, raw=raw, mean=mean, rstd=rstd, out=feats)
+        if out is None:
+            return feats
+        ops.copy2d(feats.view(B, -1), out.view(B, -1), B, self.output_shape[0] * hw)  # (rows of the wider buffer)
+        return out
+
+    def forward(self, observations, out=None, out_ctot=0, save=None):
         """observations["depth"]: (B,H,W,1) f32.  `out`: optional (B,128,4,4) channel slice of a wider
-        NCHW buffer with `out_ctot` channels (the policy passes its depth+spatial-embedding buffer)."""
+        NCHW buffer with `out_ctot` channels (the policy passes its depth+spatial-embedding buffer).
+        `save`: a dict = the differentiated pass of a trainable encoder (forward_train)."""
+        if save is not None:
+            return self.forward_train(observations, save, out, out_ctot)
         depth = observations["depth"].to(torch.float32).contiguous()
         B, H, W, Cd = depth.shape
         assert Cd == 1, "depth-only encoder"
@@ -586,9 +662,11 @@ class VlnResnetDepthEncoder(nn.Module):
     def is_blind(self):
         return self.visual_encoder.is_blind
 
-    def forward(self, observations):
+    def forward(self, observations, save=None):
         """-> (B, 192, 4, 4): visual features ++ the learned spatial embedding (a raw `.view` of the
-        (16,64) table as (64,4,4), resnet_encoders.py:97-113)."""
+        (16,64) table as (64,4,4), resnet_encoders.py:97-113).  `save`: a dict that receives the visual encoder's
+        per-layer saves (ResNetEncoder.forward_train) - the update pass of a trainable encoder fed with depth frames;
+        it stays empty when the features come cached."""
         c, h, w = self.visual_encoder.output_shape
         E = self.spatial_embeddings.embedding_dim
         if "depth_features" in observations:
@@ -600,7 +678,7 @@ class VlnResnetDepthEncoder(nn.Module):
             B = observations["depth"].shape[0]
             dev = observations["depth"].device
             sw = self.spatial_embeddings.weight
-            if not torch.is_grad_enabled():
+            if save is None and not torch.is_grad_enabled():
                 # inference: the embedding half of the output is constant between weight updates - keep one output
                 # buffer per batch size with that half filled once instead of one copy launch per step.  (Created
                 # outside graph capture only: a buffer from a graph's private pool must not outlive that graph.)
@@ -617,7 +695,7 @@ class VlnResnetDepthEncoder(nn.Module):
                     self.visual_encoder(observations, out=ent[1][:, :c], out_ctot=c + E)
                     return ent[1]
             out = torch.empty((B, c + E, h, w), dtype=torch.float32, device=dev)
-            self.visual_encoder(observations, out=out[:, :c], out_ctot=c + E)
+            self.visual_encoder(observations, out=out[:, :c], out_ctot=c + E, save=save)
         ops.copy2d(self.spatial_embeddings.weight.view(1, -1), out.view(B, -1)[:, c * h * w:], B, E * h * w,
                    broadcast_rows=True)
         return out

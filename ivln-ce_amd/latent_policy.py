@@ -129,6 +129,7 @@ class LatentCMANet(Net):
         self.depth_encoder = VlnResnetDepthEncoder(
             observation_space, output_size=model_config.DEPTH_ENCODER.output_size,
             checkpoint=model_config.DEPTH_ENCODER.ddppo_checkpoint, backbone=model_config.DEPTH_ENCODER.backbone,
+            trainable=bool(model_config.DEPTH_ENCODER.trainable),  # (see MapCMANet: the key reaches the encoder here)
             spatial_output=True,
         )
         assert model_config.RGB_ENCODER.cnn_type in ["TorchVisionResNet50"], \
@@ -250,7 +251,11 @@ class LatentCMANet(Net):
         else:
             txt, lengths = self.instruction_encoder(observations, s_txt)  # (rows, Ct, L), zero beyond each length
             tk = None
-        dep = self.depth_encoder(observations)                         # (rows, 192, 4, 4)
+        # (a trainable depth encoder fed with frames leaves its per-layer saves for train.depth_encoder_backward; an
+        #  ablated branch is multiplied by 0: its encoder's gradient is exactly zero, nothing is saved)
+        s_dep = {} if (save is not None and not mc.ablate_depth and "depth_features" not in observations
+                       and self.depth_encoder.visual_encoder.trains) else None
+        dep = self.depth_encoder(observations, save=s_dep) if s_dep is not None else self.depth_encoder(observations)  # (rows, 192, 4, 4)
         rgb = self.rgb_encoder(observations)                           # (rows, 2112, 4, 4)
         if mc.ablate_instruction:
             txt = torch.zeros_like(txt)
@@ -344,12 +349,13 @@ class LatentCMANet(Net):
             save.update(txt=s_txt, g1=s_g1, g2=s_g2, dep=dep, rgb=rgb, rgb_mean=rgb_mean, txt_out=txt, state_in=state_in,
                         x2=x2, q1=q1, tk=tk, a_txt=a_txt, rkv=rkv, dkv=dkv, q2=q2, a_rgb=a_rgb, a_dep=a_dep, c2=c2,
                         cat=cat, feats=feats, rows=rows, N=N, L=L, P=P, offs=(o_txt, o_rgb, o_dep, o_prev),
-                        act_masks=act_u8, prev_actions=prev_actions)
+                        act_masks=act_u8, prev_actions=prev_actions, depth_enc=s_dep or None)
         return feats, rnn_out
 
     def backward_hip(self, S, d_feats):
         """Gradients of every trainable parameter given d(loss)/d(features): the hand-written HIP backward of
-        `forward_hip` (the frozen RGB / depth ResNets are not traversed; their learned spatial embeddings are)."""
+        `forward_hip` (the frozen RGB ResNet is not traversed, the depth ResNet only when it trains; their learned spatial
+        embeddings are)."""
         from . import train as _train
         from .train import _conv1d_backward, _gru_backward, instruction_backward
 
@@ -448,6 +454,9 @@ class LatentCMANet(Net):
         d_dep = _conv1d_backward(self.depth_kv, d_dkv.view(rows, -1, 1, P), dep.view(rows, Cd, 1, P),
                                  d_dep.view(rows, Cd, 1, P), G)
         G[se_d.weight] = ops.colsum(d_dep.view(rows, -1)[:, (Cd - Ed) * P:]).view_as(se_d.weight)
+        if S.get("depth_enc"):  # MODEL.DEPTH_ENCODER.trainable: through the GroupNorm ResNet (RGB_ENCODER.trainable: still not trained)
+            _train.depth_encoder_backward(self.depth_encoder.visual_encoder, S["depth_enc"],
+                                          d_dep.view(rows, Cd, P)[:, :Cd - Ed], G)
 
         if G_txt is None:
             instruction_backward(self.instruction_encoder, S["txt"], d_txt, rows, L, G)

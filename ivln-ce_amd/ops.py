@@ -849,10 +849,11 @@ def kv_linear(feat, w_kv, b_kv, w_lin, b_lin, lin_out, relu=True):
 
 
 def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, residual=None, out=None, y_img_stride=0,
-              r_img_stride=0, x2=None, gamma2=None, beta2=None):
+              r_img_stride=0, x2=None, gamma2=None, beta2=None, save_mean=None, save_rstd=None):
     """x: NCHW tensor or a `Deferred` conv output (slab reduction fused).  `out` may be a channel slice
     of a wider NCHW buffer (y_img_stride = its image stride).  x2 (+gamma2, beta2): a second operand that is
-    group-normalised (same groups) and added before the ReLU."""
+    group-normalised (same groups) and added before the ReLU.  save_mean / save_rstd: (N * groups) tensors that receive
+    the statistics of `x` (both or none; what groupnorm_bwd reads)."""
     if isinstance(x, Deferred):
         N, Cc, H, W = x.N, x.C, x.H, x.W
         HW = H * W
@@ -865,11 +866,16 @@ def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, residual=None, out=N
         dev = x.device
     if out is None:
         out = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
+    if (save_mean is None) != (save_rstd is None):
+        raise _lib.IvlnError("groupnorm: save_mean and save_rstd come together")
+    if save_mean is not None and (save_mean.numel() != N * groups or save_rstd.numel() != N * groups):
+        raise _lib.IvlnError("groupnorm: save_mean / save_rstd hold N * groups values")
+    sm, sr = (None, None) if save_mean is None else (dptr(save_mean), dptr(save_rstd))
     if x2 is None:
         check(
             _L().ivln_groupnorm_f32(xp, dptr(gamma), dptr(beta), _p(residual), _p(out), N, Cc, HW, groups, eps,
-                                    int(bool(relu)), x_img, x_chan, splits, slab, y_img_stride, r_img_stride, None,
-                                    None, stream_ptr()),
+                                    int(bool(relu)), x_img, x_chan, splits, slab, y_img_stride, r_img_stride, sm,
+                                    sr, stream_ptr()),
             "ivln_groupnorm_f32",
         )
         return out
@@ -884,7 +890,7 @@ def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, residual=None, out=N
                                       vp, vp, vp, vp, i64, i64, i32, i64, vp]
     check(
         L.ivln_groupnorm2_f32(xp, dptr(gamma), dptr(beta), _p(residual), _p(out), N, Cc, HW, groups, eps,
-                              int(bool(relu)), x_img, x_chan, splits, slab, y_img_stride, r_img_stride, None, None,
+                              int(bool(relu)), x_img, x_chan, splits, slab, y_img_stride, r_img_stride, sm, sr,
                               x2p, dptr(gamma2), dptr(beta2), x2_img, x2_chan, splits2, slab2, stream_ptr()),
         "ivln_groupnorm2_f32",
     )
@@ -1863,6 +1869,60 @@ def weight_flip_transpose(w):
     wt = torch.empty((I, O, KH, KW), dtype=torch.float32, device=w.device)
     check(_T().ivln_weight_flip_transpose_f32(dptr(w), dptr(wt), O, I, KH, KW, stream_ptr()),
           "ivln_weight_flip_transpose_f32")
+    return wt
+
+
+def groupnorm_bwd(dy, x, mean, rstd, gamma, groups, out=None, want_dz=False, dx=None, dgamma=None, dbeta=None):
+    """Backward of ops.groupnorm (+ the ReLU behind it): dy, x (N, C, H, W) - the upstream gradient and the raw input the
+    forward normalised - mean / rstd (N * groups) as the forward saved them; `out`: the block's activated output, whose sign
+    masks dy (None: no ReLU between).  -> (dx, dgamma, dbeta, dz): dz = the masked gradient when `want_dz` (True, or the
+    tensor that receives it), else None.  dx / dgamma / dbeta: optional destinations.
+    The tensors may be views (a storage offset takes the 4-byte form of the kernel) but have to be dense."""
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // max(N * Cc, 1)
+    dz = want_dz if torch.is_tensor(want_dz) else None
+    for t in (dy, x, out, dx, dz):
+        if t is not None and (not t.is_contiguous() or t.shape != x.shape):
+            raise _lib.IvlnError("groupnorm_bwd: dy, x, out, dx and dz are dense tensors of one shape")
+    dev = x.device
+    if dx is None:
+        dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    if dz is None and want_dz:
+        dz = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    if dgamma is None:
+        dgamma = torch.empty((Cc,), dtype=torch.float32, device=dev)
+    if dbeta is None:
+        dbeta = torch.empty((Cc,), dtype=torch.float32, device=dev)
+    key = (str(dev), stream_ptr(), "gn_bwd")
+    ws = _colsum_ws.get(key)
+    if ws is None or ws.numel() < 2 * N * Cc:
+        ws = _colsum_ws[key] = torch.empty(max(2 * N * Cc, 1 << 16), dtype=torch.float32, device=dev)
+    L = _T()
+    L.ivln_groupnorm_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]
+    check(L.ivln_groupnorm_bwd_f32(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(out), N, Cc, HW, groups, _p(dx), _p(dz),
+                                   dptr(dgamma), dptr(dbeta), dptr(ws), ws.numel(), stream_ptr()), "ivln_groupnorm_bwd_f32")
+    return dx, dgamma, dbeta, dz
+
+
+def maxpool3s2_bwd(dy, x):
+    """Backward of nn.MaxPool2d(3, 2, 1): x (N, C, H, W) the saved input of the pool, dy (N, C, Ho, Wo) -> dx like x."""
+    N, Cc, H, W = x.shape
+    if tuple(dy.shape) != (N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1) or not dy.is_contiguous() or not x.is_contiguous():
+        raise _lib.IvlnError("maxpool3s2_bwd: dy is the dense (N, C, (H-1)//2+1, (W-1)//2+1) gradient of a dense x")
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    L = _T()
+    L.ivln_maxpool3s2_bwd_f32.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    check(L.ivln_maxpool3s2_bwd_f32(_p(dy), _p(x), N * Cc, H, W, _p(dx), stream_ptr()), "ivln_maxpool3s2_bwd_f32")
+    return dx
+
+
+def weight_oi_transpose(w):
+    """(O, I, kh, kw) -> (I, O, kh, kw), taps in place: what conv_transpose2d takes as the input gradient's weight."""
+    O, I, KH, KW = w.shape
+    wt = torch.empty((I, O, KH, KW), dtype=torch.float32, device=w.device)
+    L = _T()
+    L.ivln_weight_oi_transpose_f32.argtypes = [vp, vp, i32, i32, i32, vp]
+    check(L.ivln_weight_oi_transpose_f32(dptr(w), dptr(wt), O, I, KH * KW, stream_ptr()), "ivln_weight_oi_transpose_f32")
     return wt
 
 

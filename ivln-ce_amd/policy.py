@@ -116,6 +116,9 @@ class MapCMANet(Net):
             output_size=model_config.DEPTH_ENCODER.output_size,
             checkpoint=model_config.DEPTH_ENCODER.ddppo_checkpoint,
             backbone=model_config.DEPTH_ENCODER.backbone,
+            # (the reference's policies never hand the key to the encoder: there it only stops the trainers' feature
+            #  cache and the ResNet stays frozen; here a trainable encoder trains - train.depth_encoder_backward)
+            trainable=bool(model_config.DEPTH_ENCODER.trainable),
             spatial_output=True,
         )
         self.prev_action_embedding = nn.Embedding(num_actions + 1, 32)
@@ -346,9 +349,14 @@ class MapCMANet(Net):
             m = torch.zeros_like(m)
         return m, self._kv_branch(m, self.map_kv, self.map_linear[1], state_in[:, geo.d_out:geo.d_out + geo.m_out])
 
-    def _dep_branch(self, observations, state_in):
-        """Depth ResNet -> (features (rows,192,4,4), k/v); depth_linear fills its columns of state_in."""
-        d = self.depth_encoder(observations)
+    def _dep_branch(self, observations, state_in, sv=None):
+        """Depth ResNet -> (features (rows,192,4,4), k/v); depth_linear fills its columns of state_in.  `sv`: a dict of the
+        update pass that receives the visual encoder's per-layer saves when that encoder trains on depth frames
+        (MODEL.DEPTH_ENCODER.trainable) and the branch is not ablated (its features are multiplied by 0 then: the
+        encoder's gradient is exactly zero and nothing is saved); it stays empty otherwise."""
+        want = (sv is not None and not self.model_config.ablate_depth and "depth_features" not in observations
+                and self.depth_encoder.visual_encoder.trains)
+        d = self.depth_encoder(observations, save=sv) if want else self.depth_encoder(observations)
         if self.model_config.ablate_depth:
             d = torch.zeros_like(d)
         return d, self._kv_branch(d, self.dep_kv, self.depth_linear[1], state_in[:, :self.step_geometry.d_out])
@@ -441,6 +449,7 @@ class MapCMANet(Net):
         # (the fused head is ONE step of `rows` states: a time-major batch over fewer states takes the unfused chain)
         fused_head = self._fused_head_eligible(observations, save) and masks_u8.shape[0] == rnn_states.shape[0]
         s_txt, s_map = ({}, []) if save is not None else (None, None)
+        s_dep = {} if save is not None else None  # (filled only by a trainable depth encoder: _dep_branch)
 
         # update batches: the instruction of a trajectory is the same at every timestep, so the loader hands over the
         # UNIQUE token rows and each row's index into them (trainers.PrefetchLoader); the encoder, text_k and their
@@ -461,7 +470,7 @@ class MapCMANet(Net):
                     txt3 = self._txt_branch(observations, fused_head, s_txt, inv)
             else:
                 txt3 = self._txt_branch(observations, fused_head, s_txt, inv)
-            dep2 = self._dep_branch(observations, state_in)
+            dep2 = self._dep_branch(observations, state_in, s_dep)
             map2 = self._map_branch(observations, state_in, s_map)
             if overlap:
                 cur.wait_stream(st)
@@ -483,7 +492,7 @@ class MapCMANet(Net):
         self._prev_embed(prev_actions, masks_u8, state_in, x2)
         feats, rnn_out = self._head(rnn_states, masks_u8, state_in, x2, txt3, dep2, map2, fused_head, rnn_out, save, inv)
         if save is not None:
-            save.update(txt=s_txt, map=s_map, N=rnn_states.shape[0], prev_actions=prev_actions,
+            save.update(txt=s_txt, map=s_map, depth_enc=s_dep or None, N=rnn_states.shape[0], prev_actions=prev_actions,
                         depth_from_features="depth_features" in observations)
         return feats, rnn_out
 

@@ -3,7 +3,8 @@
 `MapCMAForwardFn` wraps the whole net forward (policy.MapCMANet.forward_hip) in ONE
 torch.autograd.Function: autograd is only the plumbing that hands us d(features) and accumulates
 the parameter gradients we return; every gradient is computed by hand-written HIP kernels
-(csrc/train_ops.hip for the element/recurrence parts, csrc/gemm_conv.hip for every dX / dW GEMM).
+(csrc/train_ops.hip for the element/recurrence parts, csrc/gemm_conv.hip for every dX / dW GEMM, csrc/depth_bwd.hip
+for the depth ResNet when MODEL.DEPTH_ENCODER.trainable is set).
 So the reference's `loss.backward()` (ivlnce_baselines/common/base_il_trainer.py:211) works on
 this policy unchanged, and `update_agent` below is the all-HIP version of `_update_agent`
 (:173-219) with fused inflection-weighted CE, flat-bucket Adam and one RCCL all-reduce.
@@ -219,6 +220,75 @@ def instruction_backward(ie, st, d_txt, rows, L, G):
         G[ie.embedding_layer.weight] = g
 
 
+# ------------------------------------------------------------------------------------------------
+# depth ResNet (MODEL.DEPTH_ENCODER.trainable)
+# ------------------------------------------------------------------------------------------------
+def _gn_backward(gn, layer, dy, G, out=None, want_dz=False):
+    """Backward of one saved GroupNorm (+ ReLU) layer (encoders._gn_train): fills G for its affine pair, returns
+    (d(raw conv output), dz | None)."""
+    dx, dgamma, dbeta, dz = ops.groupnorm_bwd(dy, layer["raw"], layer["mean"], layer["rstd"], gn.weight, gn.num_groups,
+                                              out=out, want_dz=want_dz)
+    G[gn.weight], G[gn.bias] = dgamma, dbeta
+    return dx, dz
+
+
+def _conv_backward(conv, dy, x, G, need_dx=True, residual=None):
+    """Weight gradient of a bias-free conv into G and its input gradient (+ residual) through the GEMM families: stride 1
+    as a conv over the flipped, transposed weights; stride 2 (3x3 pad 1, 1x1) as a transposed conv with output padding 1."""
+    w = conv.weight
+    O, I, k, _ = w.shape
+    s, p = conv.stride[0], conv.padding[0]
+    G[w] = ops.conv2d_bwd_weight(dy, x, k, k, s, p)
+    if not need_dx:
+        return None
+    if s == 1:
+        wt = ops.transpose(w.view(O, I)).view(I, O, 1, 1) if k == 1 else ops.weight_flip_transpose(w)
+        return ops.conv2d(dy, wt, pad=k - 1 - p, residual=residual, weight_is_temp=True)
+    if s != 2 or x.shape[2] != 2 * dy.shape[2] or x.shape[3] != 2 * dy.shape[3]:
+        raise ops._lib.IvlnError(f"depth encoder backward: no input gradient for a stride-{s} conv over {tuple(x.shape)}")
+    return ops.conv_transpose2d(dy, ops.weight_oi_transpose(w), 2, p, 1, residual=residual)
+
+
+def _bottleneck_backward(blk, s, d_out, G):
+    """d(block output) -> d(block input).  The tail relu(GN(c3) + GN_ds(ds) | identity) masks d_out once (dz): it is the
+    gradient of the third GroupNorm's output, of the downsample GroupNorm's output and of the identity."""
+    c = blk.convs
+    d_r3, dz = _gn_backward(c[7], s["l3"], d_out, G, out=s["out"], want_dz=True)
+    if blk.downsample is not None:
+        d_rd, _ = _gn_backward(blk.downsample[1], s["ds"], dz, G)
+        d_id = _conv_backward(blk.downsample[0], d_rd, s["x"], G)
+    else:
+        d_id = dz
+    d_a2 = _conv_backward(c[6], d_r3, s["l2"]["out"], G)
+    d_r2, _ = _gn_backward(c[4], s["l2"], d_a2, G, out=s["l2"]["out"])
+    d_a1 = _conv_backward(c[3], d_r2, s["l1"]["out"], G)
+    d_r1, _ = _gn_backward(c[1], s["l1"], d_a1, G, out=s["l1"]["out"])
+    return _conv_backward(c[0], d_r1, s["x"], G, residual=d_id)
+
+
+def depth_encoder_backward(visual_encoder, save, d_feats, G):
+    """Hand-written backward of encoders.ResNetEncoder: `save` as ResNetEncoder.forward_train left it, d_feats
+    (B, 128, 4, 4) (a channel slice of a wider gradient is fine) = d(loss)/d(encoder output).  Walks the saves in reverse
+    and fills G for all 162 tensors of the encoder; the depth image takes no gradient.  Saves are released layer by layer."""
+    ve, bb = visual_encoder, visual_encoder.backbone
+    comp = save.pop("comp")
+    B = comp["out"].shape[0]
+    d = torch.empty_like(comp["out"])
+    ops.copy2d(d_feats.reshape(B, -1) if d_feats.is_contiguous() else d_feats.view(B, -1), d.view(B, -1), B, d[0].numel())
+    d_raw, _ = _gn_backward(ve.compression[1], comp, d, G, out=comp["out"])
+    d = _conv_backward(ve.compression[0], d_raw, comp["x"], G)
+    del comp, d_raw
+    blocks = [b for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4) for b in layer]
+    saves = save.pop("blocks")
+    for blk in reversed(blocks):
+        d = _bottleneck_backward(blk, saves.pop(), d, G)
+    stem = save.pop("stem")
+    d = ops.maxpool3s2_bwd(d, stem["out"])
+    d_raw, _ = _gn_backward(bb.conv1[1], stem, d, G, out=stem["out"])
+    _conv_backward(bb.conv1[0], d_raw, stem["x"], G, need_dx=False)
+    return G
+
+
 _ZEROS = {}
 
 
@@ -318,7 +388,7 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     G[emb.weight] = ops.prev_action_embed_bwd(S["prev_actions"], S["masks"], d_state_in[:, d_out_dep + m_out:],
                                               dx2[:, o_prev:], emb.num_embeddings)
 
-    # ---- depth branch: depth_linear + dep_kv -> spatial embedding (visual encoder is frozen) --------
+    # ---- depth branch: depth_linear + dep_kv -> spatial embedding (-> the depth ResNet when it trains) --------
     dep, mp = S["dep"], S["mp"]
     Cd, Cm = dep.shape[1], mp.shape[1]
     dl, ml = net.depth_linear[1], net.map_linear[1]
@@ -331,6 +401,8 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     se = net.depth_encoder.spatial_embeddings
     c_vis = Cd - se.embedding_dim
     G[se.weight] = _colsum(d_dep.view(rows, -1)[:, c_vis * P:]).view_as(se.weight)
+    if S.get("depth_enc"):  # MODEL.DEPTH_ENCODER.trainable: the forward took ResNetEncoder.forward_train
+        depth_encoder_backward(net.depth_encoder.visual_encoder, S["depth_enc"], d_dep.view(rows, Cd, P)[:, :c_vis], G)
 
     # ---- map branch: map_linear + map_kv -> map CNN -----------------------------------------------
     d_pre_m = ops.relu_bwd(d_state_in[:, d_out_dep:d_out_dep + m_out], state_in[:, d_out_dep:d_out_dep + m_out])
