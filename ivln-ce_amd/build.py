@@ -28,6 +28,7 @@ SOURCES = {
     "nn_ops.hip": [],
     "train_ops.hip": [],
     "depth_bwd.hip": [],
+    "rgb_bwd.hip": [],
     "dtw.cpp": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -47,6 +48,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_hip.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_rednet_glue.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_depth_bwd.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_rgb_bwd.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

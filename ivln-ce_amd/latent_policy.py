@@ -63,7 +63,9 @@ class TorchVisionResNet50(nn.Module):
     def is_blind(self):
         return False
 
-    def forward(self, observations) -> Tensor:
+    def forward(self, observations, save=None) -> Tensor:
+        """`save`: a dict that receives the per-layer saves of `cnn` (_ResNet50Body.forward_train) - the update pass of a
+        trainable encoder fed with rgb frames; it stays empty when the features come cached."""
         c, E = self.resnet_layer_size, self.spatial_embeddings.embedding_dim
         if "rgb_features" in observations:
             feats = observations["rgb_features"].to(torch.float32).contiguous()
@@ -75,7 +77,10 @@ class TorchVisionResNet50(nn.Module):
             if not rgb.is_cuda:
                 raise RuntimeError("HIP hot path needs GPU tensors (no CPU fallback)")
             B = rgb.shape[0]
-            self.cnn(rgb)  # a module call, so the trainers' forward hook on `.cnn` sees the (B,2048,4,4) features
+            if save is not None:
+                self.cnn.forward_train(rgb, save)  # (a trainable encoder's features are not cached: no hook to serve)
+            else:
+                self.cnn(rgb)  # a module call, so the trainers' forward hook on `.cnn` sees the (B,2048,4,4) features
             out = self.cnn.full_output
         # the (16, 64) table viewed as (1, 64, 4, 4): a reshape of row-major memory, not a transpose
         ops.copy2d(self.spatial_embeddings.weight.view(1, -1), out.view(B, -1)[:, c * 16:], B, E * 16, broadcast_rows=True)
@@ -108,6 +113,78 @@ class _ResNet50Body(nn.Sequential):
         self.full_output = out
         return out[:, :c]
 
+    @property
+    def trains(self):
+        """A parameter of the network takes a gradient (MODEL.RGB_ENCODER.trainable, resnet_encoders.py:141-143)."""
+        return any(p.requires_grad for p in self.parameters())
+
+    def forward_train(self, rgb: Tensor, save) -> Tensor:
+        """The update pass of a trainable encoder: the same network as `forward`, layer by layer with every conv output
+        materialised and no BatchNorm folded into a conv.  A BatchNorm in train mode normalises with the batch statistics
+        (from the conv's epilogue where the launch leaves them, else ops.bn_train_stats) and updates its running statistics
+        as torch does; one in eval mode uses the running statistics.  `save` (a dict) receives what
+        train.rgb_encoder_backward walks: save["stem"] = dict(x, raw, out, mean, rstd, train) - out = the activation in front
+        of the max-pool - save["blocks"] = one entry per bottleneck (_bottleneck_train), save["pool"] = the (H, W) in front of
+        the 4x4 average pool.  Callers take it only for a pass that will be differentiated and only when `trains`."""
+        x = ops.rgb_to_nchw(rgb.to(torch.uint8).contiguous(), 255.0)
+        stem, s, b = _conv_bn_train(x, self[0], self[1])
+        stem.update(x=x, out=ops.bn_apply(stem["raw"], s, b, relu=True))
+        save["stem"], save["blocks"] = stem, []
+        x = ops.pool2d(stem["out"], 3, 2, 1, "max")
+        for layer in (self[4], self[5], self[6], self[7]):
+            for blk in layer:
+                x = _bottleneck_train(blk, x, save["blocks"])
+        save["pool"] = tuple(x.shape[2:])
+        c = x.shape[1]
+        out = torch.empty((x.shape[0], c + self.extra_channels, 4, 4), dtype=torch.float32, device=x.device)
+        ops.adaptive_avgpool2d(x, 4, 4, out=out, out_ctot=c + self.extra_channels)
+        self.full_output = out
+        self._epoch = -1  # (the running statistics moved: `forward` folds them again)
+        return out[:, :c]
+
+
+def _conv_bn_train(x, conv, bn):
+    """conv -> the BatchNorm's scale / shift, not applied yet: (dict(raw, train[, mean, rstd]), scale, shift).  Train mode:
+    batch statistics, mean / rstd kept for the backward, running statistics and num_batches_tracked updated; eval mode:
+    the running statistics (the backward reads them from the module: dx = gamma * rstd * dz)."""
+    C = bn.num_features
+    scale = torch.empty(C, dtype=torch.float32, device=x.device)
+    shift = torch.empty(C, dtype=torch.float32, device=x.device)
+    if not bn.training:
+        raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0])
+        ops.bn_fold(bn, scale, shift)
+        return dict(raw=raw, train=False), scale, shift
+    stats = [] if ops.CONV_STATS else None
+    raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0], stats=stats)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    if stats:
+        ops.bn_stats_from_partials(stats[0][0], stats[0][1], bn, scale, shift, mean, rstd)
+    else:  # (the launch left no per-tile statistics - split K, a kernel without that epilogue: from the output)
+        ops.bn_train_stats(raw, bn, scale, shift, mean, rstd)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return dict(raw=raw, mean=mean, rstd=rstd, train=True), scale, shift
+
+
+def _bottleneck_train(blk: Bottleneck, x, save):
+    """Bottleneck.forward_hip for the differentiated pass.  Appends dict(x, l1, l2, l3, ds | None, out) to `save`; l1 / l2 =
+    dict(raw, out, ...) of a conv -> BatchNorm -> ReLU layer, l3 / ds = dict(raw, ...) of the two BatchNorms that meet in the
+    tail out = relu(bn3(c3) + bn_ds(ds) | x), one launch."""
+    l1, s, b = _conv_bn_train(x, blk.conv1, blk.bn1)
+    l1["out"] = ops.bn_apply(l1["raw"], s, b, relu=True)
+    l2, s, b = _conv_bn_train(l1["out"], blk.conv2, blk.bn2)
+    l2["out"] = ops.bn_apply(l2["raw"], s, b, relu=True)
+    l3, s, b = _conv_bn_train(l2["out"], blk.conv3, blk.bn3)
+    ds = None
+    if blk.downsample is not None:
+        ds, sd, bd = _conv_bn_train(x, blk.downsample[0], blk.downsample[1])
+        out = ops.bn_apply(l3["raw"], s, b, relu=True, x2=ds["raw"], scale2=sd, shift2=bd)
+    else:
+        out = ops.bn_apply(l3["raw"], s, b, relu=True, residual=x)
+    save.append(dict(x=x, l1=l1, l2=l2, l3=l3, ds=ds, out=out))
+    return out
+
 
 class LatentCMANet(Net):
     """latent_cma_policy.py:195-497 (inference): instruction bi-LSTM, DD-PPO depth ResNet, torchvision RGB
@@ -134,7 +211,10 @@ class LatentCMANet(Net):
         )
         assert model_config.RGB_ENCODER.cnn_type in ["TorchVisionResNet50"], \
             "RGB_ENCODER.cnn_type must be TorchVisionResNet50"
-        self.rgb_encoder = TorchVisionResNet50(output_size=model_config.RGB_ENCODER.output_size, spatial_output=True)
+        # (the reference never hands `trainable` to the encoder, latent_cma_policy.py:235-238: there the key only stops the
+        #  trainers' feature cache and the ResNet stays frozen; here a trainable encoder trains - train.rgb_encoder_backward)
+        self.rgb_encoder = TorchVisionResNet50(output_size=model_config.RGB_ENCODER.output_size,
+                                               trainable=bool(model_config.RGB_ENCODER.trainable), spatial_output=True)
         self.prev_action_embedding = nn.Embedding(num_actions + 1, 32)
         hidden_size = model_config.STATE_ENCODER.hidden_size
         self._hidden_size = hidden_size
@@ -256,7 +336,10 @@ class LatentCMANet(Net):
         s_dep = {} if (save is not None and not mc.ablate_depth and "depth_features" not in observations
                        and self.depth_encoder.visual_encoder.trains) else None
         dep = self.depth_encoder(observations, save=s_dep) if s_dep is not None else self.depth_encoder(observations)  # (rows, 192, 4, 4)
-        rgb = self.rgb_encoder(observations)                           # (rows, 2112, 4, 4)
+        # (likewise the RGB ResNet-50: saves for train.rgb_encoder_backward; ablated, its gradients are exact zeros)
+        rgb_trains = save is not None and "rgb_features" not in observations and self.rgb_encoder.cnn.trains
+        s_rgb = {} if (rgb_trains and not mc.ablate_rgb) else None
+        rgb = self.rgb_encoder(observations, save=s_rgb) if s_rgb is not None else self.rgb_encoder(observations)  # (rows, 2112, 4, 4)
         if mc.ablate_instruction:
             txt = torch.zeros_like(txt)
         if mc.ablate_depth:
@@ -350,12 +433,14 @@ class LatentCMANet(Net):
                         x2=x2, q1=q1, tk=tk, a_txt=a_txt, rkv=rkv, dkv=dkv, q2=q2, a_rgb=a_rgb, a_dep=a_dep, c2=c2,
                         cat=cat, feats=feats, rows=rows, N=N, L=L, P=P, offs=(o_txt, o_rgb, o_dep, o_prev),
                         act_masks=act_u8, prev_actions=prev_actions, depth_enc=s_dep or None)
+            if rgb_trains:  # (a frozen encoder leaves no key behind: its saves are what they were)
+                save.update(rgb_enc=s_rgb or None)
         return feats, rnn_out
 
     def backward_hip(self, S, d_feats):
         """Gradients of every trainable parameter given d(loss)/d(features): the hand-written HIP backward of
-        `forward_hip` (the frozen RGB ResNet is not traversed, the depth ResNet only when it trains; their learned spatial
-        embeddings are)."""
+        `forward_hip` (the RGB and the depth ResNet are traversed only when they train; their learned spatial embeddings
+        always are)."""
         from . import train as _train
         from .train import _conv1d_backward, _gru_backward, instruction_backward
 
@@ -445,6 +530,18 @@ class LatentCMANet(Net):
         g_se = ops.colsum(d_se.view(rows, -1)).view(Er, P)
         d_mean = ops.colsum(ops.linear_bwd_input(d_pre_r, rl.weight[:, Cr - Er:].contiguous()))  # (Er,)
         G[se_r.weight] = (g_se + d_mean.view(Er, 1) / P).reshape(se_r.weight.shape)
+        if S.get("rgb_enc"):
+            # MODEL.RGB_ENCODER.trainable: the full d(rgb)[:, :2048] = rgb_kv.weight[:, :2048]^T d_rkv + the mean's share,
+            # (rgb_linear.weight^T d_pre_r)[:, :2048] / P at each of the P positions, then through the BatchNorm ResNet-50
+            Cv = Cr - Er
+            w_vis = ops.transpose(kvw[:, :Cv].contiguous())  # (Cv, O)
+            d_lin = ops.linear_bwd_input(d_pre_r, rl.weight[:, :Cv].contiguous())  # (rows, Cv)
+            d_vis = ops.conv2d(d_rkv.view(rows, -1, 1, P), w_vis.view(Cv, -1, 1, 1), weight_is_temp=True,
+                               residual=ops.adaptive_avgpool2d_bwd(d_lin.view(rows, Cv, 1, 1), 1, P))
+            _train.rgb_encoder_backward(self.rgb_encoder.cnn, S["rgb_enc"], d_vis.view(rows, Cv, rgb.shape[2], rgb.shape[3]), G)
+        elif "rgb_enc" in S:  # a trainable encoder behind ablate_rgb: its features were multiplied by 0
+            for p in self.rgb_encoder.cnn.parameters():
+                G[p] = _train._zeros_like_cached(p)
 
         # ---- depth branch: depth_linear + depth_kv -> spatial embedding
         d_pre_d = ops.relu_bwd(d_state_in[:, r_out:r_out + d_out], state_in[:, r_out:r_out + d_out])
@@ -454,7 +551,7 @@ class LatentCMANet(Net):
         d_dep = _conv1d_backward(self.depth_kv, d_dkv.view(rows, -1, 1, P), dep.view(rows, Cd, 1, P),
                                  d_dep.view(rows, Cd, 1, P), G)
         G[se_d.weight] = ops.colsum(d_dep.view(rows, -1)[:, (Cd - Ed) * P:]).view_as(se_d.weight)
-        if S.get("depth_enc"):  # MODEL.DEPTH_ENCODER.trainable: through the GroupNorm ResNet (RGB_ENCODER.trainable: still not trained)
+        if S.get("depth_enc"):  # MODEL.DEPTH_ENCODER.trainable: through the GroupNorm ResNet
             _train.depth_encoder_backward(self.depth_encoder.visual_encoder, S["depth_enc"],
                                           d_dep.view(rows, Cd, P)[:, :Cd - Ed], G)
 

@@ -1926,6 +1926,72 @@ def weight_oi_transpose(w):
     return wt
 
 
+def bn_apply(x, scale, shift, relu=False, residual=None, x2=None, scale2=None, shift2=None, out=None):
+    """out = [relu](x * scale[c] + shift[c] [+ residual] [+ x2 * scale2[c] + shift2[c]]): BatchNorm with folded statistics
+    over a materialised conv output x (N, C, H, W), and the bottleneck tail with an identity (`residual`) or a second
+    normalised operand (`x2`, the downsample branch).  Dense tensors of one shape."""
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // max(N * Cc, 1)
+    for t in (x, residual, x2, out):
+        if t is not None and (not t.is_contiguous() or t.shape != x.shape):
+            raise _lib.IvlnError("bn_apply: x, residual, x2 and out are dense tensors of one shape")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    L = _T()
+    L.ivln_bn_apply_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    check(L.ivln_bn_apply_f32(_p(x), _p(scale), _p(shift), _p(residual), _p(x2), _p(scale2), _p(shift2), N, Cc, HW,
+                              int(bool(relu)), _p(out), stream_ptr()), "ivln_bn_apply_f32")
+    return out
+
+
+def bn_bwd(dy, x, mean, rstd_or_var, gamma, train=True, eps=1e-5, out=None, want_dz=False, dx=None, dgamma=None, dbeta=None):
+    """Backward of BatchNorm2d (+ the ReLU behind it): dy, x (N, C, H, W) - the upstream gradient and the raw conv output the
+    forward normalised.  train: mean / rstd_or_var (C) = the batch mean / rstd the forward saved; else running_mean /
+    running_var (and `eps`), dx = gamma * rstd * dz.  `out`: the activated output, whose sign masks dy (None: no ReLU
+    between).  -> (dx, dgamma, dbeta, dz): dz = the masked gradient when `want_dz` (True, or the tensor that receives it - dy
+    itself is allowed), else None.  dx (may be `out`: it is overwritten) / dgamma / dbeta: optional destinations."""
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // max(N * Cc, 1)
+    dz = want_dz if torch.is_tensor(want_dz) else None
+    for t in (dy, x, out, dx, dz):
+        if t is not None and (not t.is_contiguous() or t.shape != x.shape):
+            raise _lib.IvlnError("bn_bwd: dy, x, out, dx and dz are dense tensors of one shape")
+    dev = x.device
+    if dx is None:
+        dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    if dz is None and want_dz:
+        dz = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    if dgamma is None:
+        dgamma = torch.empty((Cc,), dtype=torch.float32, device=dev)
+    if dbeta is None:
+        dbeta = torch.empty((Cc,), dtype=torch.float32, device=dev)
+    need = 4 * Cc * min(N, 64) + 2  # (double partials of two sums per channel and slice of the images)
+    key = (str(dev), stream_ptr(), "bn_bwd")
+    ws = _colsum_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _colsum_ws[key] = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=dev)
+    L = _T()
+    L.ivln_bn_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i64, vp]
+    check(L.ivln_bn_bwd_f32(_p(dy), _p(x), _p(mean), _p(rstd_or_var), _p(gamma), _p(out), N, Cc, HW, int(bool(train)), eps,
+                            _p(dx), _p(dz), dptr(dgamma), dptr(dbeta), dptr(ws), ws.numel(), stream_ptr()), "ivln_bn_bwd_f32")
+    return dx, dgamma, dbeta, dz
+
+
+def adaptive_avgpool2d_bwd(dy, H, W, out_ctot=0):
+    """Backward of ops.adaptive_avgpool2d: dy (N, C, OH, OW), dense or a channel slice of an (N, out_ctot, OH, OW) buffer ->
+    dx (N, C, H, W)."""
+    N, Cc, OH, OW = dy.shape
+    want = (max(out_ctot, Cc) * OH * OW, OH * OW, OW, 1)
+    if any(dy.shape[i] > 1 and dy.stride(i) != want[i] for i in range(4)):
+        raise _lib.IvlnError("adaptive_avgpool2d_bwd: dy is (N, C, OH, OW) inside an (N, out_ctot, OH, OW) buffer")
+    dx = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dy.device)
+    L = _T()
+    L.ivln_adaptive_avgpool2d_bwd_f32.argtypes = [vp, i32, i32, i32, i32, i32, i32, i64, vp, vp]
+    check(L.ivln_adaptive_avgpool2d_bwd_f32(_p(dy), N, Cc, H, W, OH, OW, want[0], _p(dx), stream_ptr()),
+          "ivln_adaptive_avgpool2d_bwd_f32")
+    return dx
+
+
 def attn_bwd(dout, attn_p, q, k, v, scale, dq, dk, dv, row_index=None):
     """dk / dv are per ROW (rows, C, I) even when rows share key/value images through row_index (index_sum folds them)."""
     rows, Ck = q.shape

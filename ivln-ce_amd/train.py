@@ -4,7 +4,8 @@
 torch.autograd.Function: autograd is only the plumbing that hands us d(features) and accumulates
 the parameter gradients we return; every gradient is computed by hand-written HIP kernels
 (csrc/train_ops.hip for the element/recurrence parts, csrc/gemm_conv.hip for every dX / dW GEMM, csrc/depth_bwd.hip
-for the depth ResNet when MODEL.DEPTH_ENCODER.trainable is set).
+for the depth ResNet when MODEL.DEPTH_ENCODER.trainable is set, csrc/rgb_bwd.hip for the RGB ResNet-50 when
+MODEL.RGB_ENCODER.trainable is).
 So the reference's `loss.backward()` (ivlnce_baselines/common/base_il_trainer.py:211) works on
 this policy unchanged, and `update_agent` below is the all-HIP version of `_update_agent`
 (:173-219) with fused inflection-weighted CE, flat-bucket Adam and one RCCL all-reduce.
@@ -286,6 +287,58 @@ def depth_encoder_backward(visual_encoder, save, d_feats, G):
     d = ops.maxpool3s2_bwd(d, stem["out"])
     d_raw, _ = _gn_backward(bb.conv1[1], stem, d, G, out=stem["out"])
     _conv_backward(bb.conv1[0], d_raw, stem["x"], G, need_dx=False)
+    return G
+
+
+# ------------------------------------------------------------------------------------------------
+# RGB ResNet-50 (MODEL.RGB_ENCODER.trainable)
+# ------------------------------------------------------------------------------------------------
+def _bn_backward(bn, layer, dy, G, out=None, want_dz=False):
+    """Backward of one saved BatchNorm (+ ReLU) layer (latent_policy._conv_bn_train): fills G for its affine pair, returns
+    (d(raw conv output), dz | None).  A layer that ran in eval mode reads the module's running statistics.  With `out` (the
+    activated output: the ReLU mask) the result overwrites it - nothing reads that activation afterwards."""
+    mean, rv = (layer["mean"], layer["rstd"]) if layer["train"] else (bn.running_mean, bn.running_var)
+    dx, dgamma, dbeta, dz = ops.bn_bwd(dy, layer["raw"], mean, rv, bn.weight, train=layer["train"], eps=bn.eps, out=out,
+                                       want_dz=want_dz, dx=out)
+    G[bn.weight], G[bn.bias] = dgamma, dbeta
+    return dx, dz
+
+
+def _bn_bottleneck_backward(blk, s, d_out, G):
+    """d(block output) -> d(block input), rednet.Bottleneck as latent_policy._bottleneck_train saved it.  The tail
+    relu(bn3(c3) + bn_ds(ds) | identity) masks d_out once, in place (dz): it is the gradient of bn3's output, of the
+    downsample BatchNorm's output and of the identity."""
+    d_r3, dz = _bn_backward(blk.bn3, s["l3"], d_out, G, out=s["out"], want_dz=d_out)
+    if blk.downsample is not None:
+        d_rd, _ = _bn_backward(blk.downsample[1], s["ds"], dz, G)
+        d_id = _conv_backward(blk.downsample[0], d_rd, s["x"], G)
+    else:
+        d_id = dz
+    d_a2 = _conv_backward(blk.conv3, d_r3, s["l2"]["out"], G)
+    d_r2, _ = _bn_backward(blk.bn2, s["l2"], d_a2, G, out=s["l2"]["out"])
+    d_a1 = _conv_backward(blk.conv2, d_r2, s["l1"]["out"], G)
+    d_r1, _ = _bn_backward(blk.bn1, s["l1"], d_a1, G, out=s["l1"]["out"])
+    return _conv_backward(blk.conv1, d_r1, s["x"], G, residual=d_id)
+
+
+def rgb_encoder_backward(cnn, save, d_feats, G):
+    """Hand-written backward of latent_policy._ResNet50Body: `save` as its forward_train left it, d_feats (B, 2048, 4, 4)
+    dense or a channel slice of a wider (B, C, 4, 4) gradient = d(loss)/d(features).  Walks the saves in reverse - adaptive
+    average pool, 16 bottlenecks, max-pool, stem - and fills G for every parameter of `cnn`; the image takes no gradient.
+    Saves are released layer by layer."""
+    H, W = save.pop("pool")
+    d = ops.adaptive_avgpool2d_bwd(d_feats, H, W, out_ctot=d_feats.stride(0) // (d_feats.shape[2] * d_feats.shape[3]))
+    blocks = [b for layer in (cnn[4], cnn[5], cnn[6], cnn[7]) for b in layer]
+    saves = save.pop("blocks")
+    for blk in reversed(blocks):
+        d = _bn_bottleneck_backward(blk, saves.pop(), d, G)
+    stem = save.pop("stem")
+    d = ops.maxpool3s2_bwd(d, stem["out"])
+    d_raw, _ = _bn_backward(cnn[1], stem, d, G, out=stem["out"])
+    _conv_backward(cnn[0], d_raw, stem["x"], G, need_dx=False)
+    names = dict(cnn.named_parameters())
+    missing = [k for k, p in names.items() if p not in G]
+    assert not missing, f"rgb_encoder_backward left {len(missing)} of {len(names)} parameters without a gradient: {missing[:3]}"
     return G
 
 
