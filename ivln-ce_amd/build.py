@@ -25,6 +25,7 @@ SOURCES = {
     "state_rnn.hip": [],
     # (GRU instruction encoder: its register arrays are indexed by fully unrolled loops only - 0 scratch bytes)
     "instr_rnn.hip": [],
+    "text_feat.hip": [],
     "nn_ops.hip": [],
     "train_ops.hip": [],
     "depth_bwd.hip": [],
@@ -49,6 +50,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_rednet_glue.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_depth_bwd.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_rgb_bwd.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_text_feat.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

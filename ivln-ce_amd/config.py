@@ -356,6 +356,10 @@ def _task_defaults() -> Config:
     T.TASK.SDTW = CN()
     T.TASK.SDTW.TYPE = "SDTW"
     T.TASK.INSTRUCTION_SENSOR_UUID = "instruction"
+    # "rxr_instruction": pre-computed text features (habitat_extensions/sensors.py:119, 512 x 768 BERT features); the
+    # feature width is MODEL.INSTRUCTION_ENCODER.embedding_size
+    T.TASK.RXR_INSTRUCTION_SENSOR = CN()
+    T.TASK.RXR_INSTRUCTION_SENSOR.max_text_len = 512
     T.DATASET = CN()
     T.DATASET.TYPE = "VLN-CE-v1"
     T.DATASET.SPLIT = "train"

@@ -184,6 +184,17 @@ class InstructionEncoder(nn.Module):
         return self.config.hidden_size * (1 + int(bool(self.config.bidirectional)))
 
     @property
+    def uses_features(self):
+        """The sensor delivers pre-computed (L, E) text features, not token ids: any sensor_uuid but "instruction"
+        (instruction_encoder.py:34-45) - no embedding layer exists and W_ih reads the features directly."""
+        return self.config.sensor_uuid != "instruction"
+
+    @property
+    def obs_key(self):
+        """The observation the encoder reads (instruction_encoder.py:70-76)."""
+        return "rxr_instruction" if self.uses_features else "instruction"
+
+    @property
     def is_gru(self):
         return isinstance(self.encoder_rnn, nn.GRU)
 
@@ -226,28 +237,33 @@ class InstructionEncoder(nn.Module):
             c = self.__dict__["_gate_cache"] = (key, (table, nz))
         return c[1]
 
-    def step_cache(self, rows, L, device):
+    def step_cache(self, rows, L, device, feat=None):
         """The per-episode cache of a rollout batch shape (ops.InstructionStepCache), or None: switched off, a capture in
         progress that would have to create or invalidate it (the warm-up steps before a capture do that), no folded table.
         A cache made for other weights (recurrent / embedding versions, ops.WEIGHT_EPOCH) is invalidated, not rebuilt:
-        captured graphs hold its buffers.  The key names the recurrent parameters that exist for the combination."""
+        captured graphs hold its buffers.  The key names the recurrent parameters that exist for the combination.
+        `feat` = E: the feature flavour (`uses_features`), which compares (L, E) features instead of tokens."""
         if not ops.CACHE_INSTRUCTION:
             return None
         gate_key = (self.__dict__.get("_gate_cache") or (None,))[0]
         rnn = self.encoder_rnn
         ws, bs = self.dir_params("weight_hh"), self.dir_params("bias_hh")
         ps = ws + bs
+        if feat is not None:  # (no folded table: the input-side weights are read at every re-encoding, so they key the cache)
+            gate_key = ops.WEIGHT_EPOCH
+            ps = ps + self.dir_params("weight_ih") + self.dir_params("bias_ih")
         key = (gate_key,) + tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps)
         caches = self.__dict__.setdefault("_step_caches", {})
-        c = caches.get((rows, L, str(device)))
+        shape = (rows, L, str(device)) if feat is None else (rows, L, str(device), int(feat))
+        c = caches.get(shape)
         capturing = torch.cuda.is_current_stream_capturing()
         if c is None:
             if capturing:
                 return None
             if len(caches) >= 4:  # (batch shapes come and go as envs pause: keep the table small)
                 caches.pop(next(iter(caches)))
-            c = caches[(rows, L, str(device))] = ops.InstructionStepCache(rows, L, self.gates * rnn.hidden_size, rnn.hidden_size,
-                                                                          device, key, ndir=self.ndir)
+            c = caches[shape] = ops.InstructionStepCache(rows, L, self.gates * rnn.hidden_size, rnn.hidden_size, device, key,
+                                                         ndir=self.ndir, feat=feat)
         elif c.key != key:
             if capturing:
                 return None
@@ -276,6 +292,8 @@ class InstructionEncoder(nn.Module):
         Rollout steps (no `save`, no autograd): the encoding is cached per row and recomputed only where the tokens
         changed (`step_cache`; the decision is taken on the device, ops.embed_gates) - `self.last_cache` then names the
         cache whose `dirty` flags belong to this call, else it is None."""
+        if self.uses_features:
+            return self._forward_features(observations, save)
         tokens = observations["instruction"].long().contiguous()
         B, L = tokens.shape
         nd = self.ndir
@@ -299,6 +317,44 @@ class InstructionEncoder(nn.Module):
         out, sv = self._recurrence(gx_f, gx_r, lengths, B, L, save=save is not None)
         if save is not None:
             save.update(emb=emb, lengths=lengths, out=out, tokens=tokens, **sv)
+        return out, lengths
+
+
+    def _forward_features(self, observations, save=None):
+        """`forward` for pre-computed features: observations["rxr_instruction"] (B, L, E) f32 (instruction_encoder.py:74-78).  lengths = the
+        number of non-zero rows and the recurrence runs over the first `lengths[b]` rows, as pack_padded_sequence does.
+        Update pass (`save`): ops.linear_gemm per direction; save["emb"] is the feature matrix itself, no save["tokens"].
+        Rollout pass: the step cache compares features on the device (ops.text_feat_front) and only the dirty rows are
+        projected and re-run.  Cached and uncached calls share the projection kernel, so they agree byte for byte."""
+        feat = observations[self.obs_key].to(torch.float32).contiguous()
+        if feat.dim() != 3 or feat.shape[2] != self.encoder_rnn.input_size:
+            raise ValueError(f"`{self.obs_key}` must be (B, L, {self.encoder_rnn.input_size}) features, got {tuple(feat.shape)}")
+        B, L, E = feat.shape
+        nd = self.ndir
+        wih, bih = self.dir_params("weight_ih"), self.dir_params("bias_ih")
+        self.last_cache = None
+        if save is not None:
+            lengths = ops.text_feat_front(feat)
+            emb = feat.view(B * L, E)
+            gx_f = ops.linear_gemm(emb, wih[0], bih[0])
+            gx_r = ops.linear_gemm(emb, wih[1], bih[1]) if nd == 2 else None
+            out, sv = self._recurrence(gx_f, gx_r, lengths, B, L, save=True)
+            save.update(emb=emb, lengths=lengths, out=out, **sv)
+            return out, lengths
+        if feat.is_cuda and not torch.is_grad_enabled():
+            cache = self.step_cache(B, L, feat.device, feat=E)
+            if cache is not None:
+                lengths = ops.text_feat_front(feat, cache=cache)
+                ops.text_feat_gates(feat, wih[0], bih[0], dirty=cache.dirty, out=cache.gx_f)
+                if nd == 2:
+                    ops.text_feat_gates(feat, wih[1], bih[1], dirty=cache.dirty, out=cache.gx_r)
+                out, _ = self._recurrence(cache.gx_f, cache.gx_r, lengths, B, L, cache=cache)
+                self.last_cache = cache
+                return out, lengths
+        lengths = ops.text_feat_front(feat)
+        gx_f = ops.text_feat_gates(feat, wih[0], bih[0])
+        gx_r = ops.text_feat_gates(feat, wih[1], bih[1]) if nd == 2 else None
+        out, _ = self._recurrence(gx_f, gx_r, lengths, B, L)
         return out, lengths
 
 

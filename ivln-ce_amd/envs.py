@@ -50,6 +50,18 @@ def _wrap(a):
     return (a + math.pi) % (2.0 * math.pi) - math.pi
 
 
+def instruction_features(tokens, L, E):
+    """Stand-in for RxRInstructionSensor's pre-computed BERT features (habitat_extensions/sensors.py:119): an (L, E) float32
+    array that is a pure function of an instruction's token row - one standard-normal row per token (at most L), zero rows
+    past its length, drawn from a generator of its own seeded by the tokens (no other random stream moves)."""
+    tok = np.asarray(tokens, np.int64).reshape(-1)
+    n = min(int(np.count_nonzero(tok)), int(L))
+    seed = int((tok * (np.arange(tok.size, dtype=np.int64) + 1)).sum() % (2 ** 31 - 1))
+    out = np.zeros((int(L), int(E)), np.float32)
+    out[:n] = np.random.RandomState(seed).standard_normal((n, int(E))).astype(np.float32)
+    return out
+
+
 class _SynthEnv:
     def __init__(self, idx, seed, cfg, episodes_per_tour=3, n_episodes=8, min_len=6, max_len=14, with_rgb=False,
                  with_semantic=True, iterative=False):
@@ -67,6 +79,11 @@ class _SynthEnv:
         self.iterative = iterative
         self.oracle_phases, self.oracle_goal_phase = bool(it.ORACLE_PHASES), bool(it.ORACLE_GOAL_PHASE)
         self.precise_start, self.oracle_limit = bool(it.PRECISE_EPISODE_START), int(it.ORACLE_STEP_ERROR_LIMIT)
+        # TASK.INSTRUCTION_SENSOR_UUID "rxr_instruction": pre-computed (L, E) text features in place of the tokens
+        self.text_features = None
+        if cfg.TASK_CONFIG.TASK.INSTRUCTION_SENSOR_UUID == "rxr_instruction":
+            self.text_features = (int(cfg.TASK_CONFIG.TASK.RXR_INSTRUCTION_SENSOR.max_text_len),
+                                  int(cfg.MODEL.INSTRUCTION_ENCODER.embedding_size))
         self.episodes = []
         starts = np.random.RandomState(seed + 7)  # own stream: scripts / tokens / frames keep their round-1 values
         for e in range(n_episodes):
@@ -79,6 +96,9 @@ class _SynthEnv:
             start = np.array([float(idx) * 3.0 + off[0], 1.25, off[1]], np.float32)
             ep = SimpleNamespace(episode_id=f"{idx}_{e}", tour_id=f"tour{idx}_{e // episodes_per_tour}",
                                  scene_id=f"scene{idx}", script=script, tokens=tokens, start=start, start_heading=0.0)
+            if self.text_features is not None:
+                ep.features = instruction_features(tokens, *self.text_features)
+                ep.features.setflags(write=False)  # (handed out at every step without a copy)
             ep.goal = np.array(self._gt_positions(ep)[-1], np.float32)
             self.episodes.append(ep)
         self.ep_i = -1          # nothing loaded: the first reset has no previous episode
@@ -110,6 +130,9 @@ class _SynthEnv:
             "progress": np.array([min(1.0, self.t / max(1, len(ep.script)))], np.float64),
             "shortest_path_sensor": np.array([float(expert)], np.float64),
         }
+        if self.text_features is not None:
+            del obs["instruction"]
+            obs["rxr_instruction"] = ep.features
         if self.with_semantic:
             obs["semantic12"] = self.rng.randint(0, 13, size=(self.H, self.W, 1)).astype(np.uint8)
         if self.with_rgb:
@@ -321,6 +344,9 @@ class SyntheticVectorEnv:
             "progress": Box(0.0, 1.0, (1,), np.float64),
             "shortest_path_sensor": Box(0.0, 100.0, (1,), np.float64),
         }
+        if config.TASK_CONFIG.TASK.INSTRUCTION_SENSOR_UUID == "rxr_instruction":
+            del sp["instruction"]
+            sp["rxr_instruction"] = Box(-np.inf, np.inf, self._envs[0].text_features if self._envs else (512, 768), np.float32)
         if env_kw["with_rgb"]:
             r = config.TASK_CONFIG.SIMULATOR.RGB_SENSOR
             sp["rgb"] = Box(0, 255, (r.HEIGHT, r.WIDTH, 3), np.uint8)

@@ -44,6 +44,14 @@ _STEP_KEYS = ("depth", "semantic12", "rgb", "instruction", "world_robot_pose", "
               "not_done_masks", "episode_not_done_masks", "_u_sample", "_u_beta")
 
 
+def _step_keys(policy):
+    """_STEP_KEYS with the observation the policy's instruction encoder reads (InstructionEncoder.obs_key: "instruction", or
+    "rxr_instruction" for pre-computed text features)."""
+    ienc = getattr(policy.net, "instruction_encoder", None)
+    key = getattr(ienc, "obs_key", "instruction")
+    return _STEP_KEYS if key in _STEP_KEYS else _STEP_KEYS + (key,)
+
+
 def _policy_masks(batch):
     return batch.get("episode_not_done_masks", batch["not_done_masks"])
 
@@ -130,8 +138,9 @@ class GraphedRollout:
         self.deterministic = deterministic
         dev = next(policy.parameters()).device
         self.device = dev
+        step_keys = _step_keys(policy)
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_obs.items()
-                       if (k in _STEP_KEYS or k in extra_keys or not torch.is_tensor(v))}
+                       if (k in step_keys or k in extra_keys or not torch.is_tensor(v))}
         # the action kernel writes straight into the next step's previous-action buffer: deterministic steps and
         # sampled steps whose uniforms come with the observations (torch's own Categorical.sample cannot)
         self._direct_actions = deterministic or "_u_sample" in self.static

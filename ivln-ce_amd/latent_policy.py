@@ -323,7 +323,7 @@ class LatentCMANet(Net):
         if overlap:
             cur, st = torch.cuda.current_stream(), _train.side_stream(dev)
             st.wait_stream(cur)
-            _train.share_with_stream(observations.get("instruction"), st)
+            _train.share_with_stream(observations.get(self.instruction_encoder.obs_key), st)
             with torch.cuda.stream(st):
                 txt, lengths = self.instruction_encoder(observations, s_txt)
                 tk = ops.conv2d(txt.view(txt.shape[0], -1, 1, txt.shape[2]), self.text_k.weight.view(h2, -1, 1, 1),

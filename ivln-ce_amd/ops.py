@@ -1290,11 +1290,22 @@ class InstructionStepCache:
     dirty flags of the current step, and everything the instruction branch produces - gate inputs (G = gates * H wide: 4H
     for an LSTM, 3H for a GRU; no reverse set when ndir == 1), lengths, the recurrence's output (ndir * H channels), the
     folded attention operands (`fold`, allocated by the policy on first use).  Allocated OUTSIDE any stream
-    capture and shared by every graph of the policy, so that what one replayed step leaves is what the next one finds."""
+    capture and shared by every graph of the policy, so that what one replayed step leaves is what the next one finds.
+    `feat` = E: the flavour for pre-computed text features - `cache_feat (rows, L, E)` and `valid (rows,)` in place of `tokens`."""
 
-    def __init__(self, rows, L, G, H, device, key, ndir=2):
+    def __init__(self, rows, L, G, H, device, key, ndir=2, feat=None):
         self.rows, self.L, self.key, self.ndir = rows, L, key, ndir
-        self.tokens = torch.full((rows, L), -1, dtype=torch.int64, device=device)  # (-1: no row matches - everything dirty)
+        self.feat_width = feat
+        if feat is None:
+            self.tokens = torch.full((rows, L), -1, dtype=torch.int64, device=device)  # (-1: no row matches - everything dirty)
+        else:
+            # the feature flavour (sensor_uuid "rxr_instruction", `feat` = E): the (L, E) features every row encoded last and
+            # whether they are an encoding's at all, in place of the tokens; `ws` is ivln_text_feat_front_f32's scratch,
+            # zeroed here once and left zero by every launch
+            self.tokens = None
+            self.cache_feat = torch.zeros((rows, L, int(feat)), dtype=torch.float32, device=device)
+            self.valid = torch.zeros((rows,), dtype=torch.int32, device=device)
+            self.ws = torch.zeros((int(_TF().ivln_text_feat_ws_words(rows)),), dtype=torch.int32, device=device)
         self.dirty = torch.ones((rows,), dtype=torch.int32, device=device)
         self.gx_f = torch.zeros((rows * L, G), dtype=torch.float32, device=device)
         self.gx_r = torch.zeros((rows * L, G), dtype=torch.float32, device=device) if ndir == 2 else None
@@ -1306,7 +1317,10 @@ class InstructionStepCache:
 
     def invalidate(self):
         """Every row re-encodes at the next step (weights changed).  An eager fill on the current stream."""
-        self.tokens.fill_(-1)
+        if self.tokens is not None:
+            self.tokens.fill_(-1)
+        else:
+            self.valid.zero_()
 
 
 import weakref as _weakref  # noqa: E402
@@ -1320,6 +1334,76 @@ def invalidate_step_caches():
     would otherwise keep serving instruction encodings of the old weights."""
     for c in list(_STEP_CACHES):
         c.invalidate()
+
+
+_tfsigs_done = False
+
+
+def _TF():
+    """Bindings of include/ivln_text_feat.h (csrc/text_feat.hip)."""
+    global _tfsigs_done
+    L = _L()
+    if not _tfsigs_done:
+        L.ivln_text_feat_ws_words.argtypes = [i32]
+        L.ivln_text_feat_ws_words.restype = i64
+        L.ivln_text_feat_front_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.ivln_text_feat_gates_f32.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+        _tfsigs_done = True
+    return L
+
+
+def _text_feat_operand(fn, name, t, dims):
+    """The kernels of csrc/text_feat.hip index dense fp32 arrays by their shape alone: anything else is refused here."""
+    if t.dtype != torch.float32 or t.dim() != dims or not t.is_contiguous() or t.numel() == 0:
+        raise _lib.IvlnError(f"{fn}: {name} must be a contiguous non-empty float32 tensor of {dims} dimensions, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+
+
+def text_feat_front(feat, cache=None):
+    """Front end of the instruction encoder over pre-computed features (ivln_text_feat_front_f32): feat (B, L, E) f32 ->
+    lengths i32 (B), the NUMBER of rows with a non-zero element (instruction_encoder.py:77-78).  cache: the feature flavour
+    of `InstructionStepCache` - its `lengths` is the result, written only for the rows whose features differ bitwise from
+    the cached ones (or were never valid); `cache.dirty` says which, and `cache.cache_feat` takes their new features."""
+    _text_feat_operand("text_feat_front", "feat", feat, 3)
+    B, L, E = feat.shape
+    T = _TF()
+    if cache is not None:
+        if cache.feat_width != E or cache.rows != B or cache.L != L:
+            raise _lib.IvlnError(f"text_feat_front: a {cache.rows} x {cache.L} x {cache.feat_width} cache for features {tuple(feat.shape)}")
+        lengths, ws = cache.lengths, cache.ws
+        cf, va, di = dptr(cache.cache_feat), dptr(cache.valid), dptr(cache.dirty)
+    else:
+        lengths = torch.empty((B,), dtype=torch.int32, device=feat.device)
+        ws = torch.zeros((int(T.ivln_text_feat_ws_words(B)),), dtype=torch.int32, device=feat.device)
+        cf = va = di = None
+    check(T.ivln_text_feat_front_f32(dptr(feat), B, L, E, dptr(lengths), cf, va, di, dptr(ws), stream_ptr()),
+          "ivln_text_feat_front_f32")
+    return lengths
+
+
+def text_feat_gates(feat, w, bias, dirty=None, out=None):
+    """gx (B*L, G) = feat (B, L, E) . w (G, E)^T + bias for the sequences with dirty[b] != 0 (None: all) - the W_ih projection
+    of the feature path (ivln_text_feat_gates_f32); rows of the other sequences keep what `out` holds."""
+    _text_feat_operand("text_feat_gates", "feat", feat, 3)
+    _text_feat_operand("text_feat_gates", "w", w, 2)
+    B, L, E = feat.shape
+    G = w.shape[0]
+    if w.shape[1] != E:
+        raise _lib.IvlnError(f"text_feat_gates: w {tuple(w.shape)} does not multiply features of width {E}")
+    if bias is not None:
+        _text_feat_operand("text_feat_gates", "bias", bias, 1)
+        if bias.shape[0] != G:
+            raise _lib.IvlnError(f"text_feat_gates: bias of {bias.shape[0]} for {G} gate rows")
+    if dirty is not None and (dirty.dtype != torch.int32 or tuple(dirty.shape) != (B,) or not dirty.is_contiguous()):
+        raise _lib.IvlnError(f"text_feat_gates: dirty must be contiguous int32 ({B},), got {dirty.dtype} {tuple(dirty.shape)}")
+    if out is None:
+        out = torch.empty((B * L, G), dtype=torch.float32, device=feat.device)
+    _text_feat_operand("text_feat_gates", "out", out, 2)
+    if tuple(out.shape) != (B * L, G):
+        raise _lib.IvlnError(f"text_feat_gates: out {tuple(out.shape)} is not ({B * L}, {G})")
+    check(_TF().ivln_text_feat_gates_f32(dptr(feat), B, L, E, dptr(w), _p(bias), G, _p(dirty), dptr(out), stream_ptr()),
+          "ivln_text_feat_gates_f32")
+    return out
 
 
 def lstm_bidir(gx_f, gx_r, whh_f, whh_r, bhh_f, bhh_r, lengths, B, L, H, save=False, spare=1, ticket=None, cache=None,

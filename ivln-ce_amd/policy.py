@@ -234,14 +234,15 @@ class MapCMANet(Net):
         """Create everything the rollout step caches lazily BEFORE a stream capture (graphed.py): a buffer born inside
         a capture lives in that graph's private pool and must not survive in a process-wide cache."""
         head = self._fused_head_ops(self.fused_head_form)
-        if ops.CMA_STEP_MODE < 0 or "instruction" not in example_obs or head is None:
+        key = self.instruction_encoder.obs_key
+        if ops.CMA_STEP_MODE < 0 or key not in example_obs or head is None:
             return
-        rows, L = example_obs["instruction"].shape[0], example_obs["instruction"].shape[1]
+        rows, L = example_obs[key].shape[0], example_obs[key].shape[1]
         P = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
         if P > 16 or L > 512:
             return  # outside the fused head's envelope: the step takes the unfused chain
         self._cma_fold_weights()
-        head[0](rows, L, P, self._hidden_size, example_obs["instruction"].device)
+        head[0](rows, L, P, self._hidden_size, example_obs[key].device)
 
     def _init_layers(self):
         if self.model_config.PROGRESS_MONITOR.use:
@@ -272,7 +273,8 @@ class MapCMANet(Net):
         mc, geo = self.model_config, self.step_geometry
         H, h2 = self._hidden_size, self._hidden_size // 2
         P_static = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
-        L_static = observations["instruction"].shape[-1] if "instruction" in observations else 0
+        key = self.instruction_encoder.obs_key  # (tokens (rows, L); features (rows, L, E): the token axis is axis 1)
+        L_static = observations[key].shape[1] if key in observations else 0
         return (save is None and ops.CMA_STEP_MODE >= 0 and self.fused_head_form is not None
                 and not (mc.ablate_instruction or mc.ablate_depth or mc.ablate_map)
                 and P_static <= 16 and 0 < L_static <= 512
@@ -284,7 +286,8 @@ class MapCMANet(Net):
         """Instruction encoder + what the head reads the instruction through: -> (txt (rows | U, 256, L), lengths, tk),
         tk = text_k's keys, or the folded [Mq | TQb] operand when `fused_head`.  `inv`: see forward_hip."""
         mc, h2 = self.model_config, self._hidden_size // 2
-        src = observations if inv is None else {"instruction": observations["instruction_unique"]}
+        key = self.instruction_encoder.obs_key
+        src = observations if inv is None else {key: observations[key + "_unique"]}
         t, ln = self.instruction_encoder(src, sv)  # (rows | U, 256, L)
         if mc.ablate_instruction:
             t = torch.zeros_like(t)
@@ -455,8 +458,9 @@ class MapCMANet(Net):
         # UNIQUE token rows and each row's index into them (trainers.PrefetchLoader); the encoder, text_k and their
         # backward then run on U sequences instead of T*N (8-9 instead of 512 at the benched shape)
         inv = None
-        if save is not None and "instruction_index" in observations and "instruction_unique" in observations:
-            inv = observations["instruction_index"].reshape(-1).to(torch.int32).contiguous()
+        ikey = self.instruction_encoder.obs_key
+        if save is not None and ikey + "_index" in observations and ikey + "_unique" in observations:
+            inv = observations[ikey + "_index"].reshape(-1).to(torch.int32).contiguous()
 
         if side_streams is None:
             from . import train as _train
@@ -465,7 +469,7 @@ class MapCMANet(Net):
             if overlap:  # training pass: the instruction bi-LSTM runs beside the map CNN (train.py)
                 cur, st = torch.cuda.current_stream(), _train.side_stream(dev)
                 st.wait_stream(cur)
-                _train.share_with_stream((observations.get("instruction"), observations.get("instruction_unique")), st)
+                _train.share_with_stream((observations.get(ikey), observations.get(ikey + "_unique")), st)
                 with torch.cuda.stream(st):
                     txt3 = self._txt_branch(observations, fused_head, s_txt, inv)
             else:

@@ -11,6 +11,8 @@ from typing import Dict, List, Sequence, Set
 import numpy as np
 import torch
 
+from .utils import expand_once_records
+
 
 def to_constant_bin_number(weights: Dict, n_bins: int) -> List[Dict]:
     """Stable sort by decreasing weight; every item joins the bin with the smallest running sum (lowest index on
@@ -41,6 +43,7 @@ def tour_collate(samples):
     (tour_dataset.py:20-104): observations padded with 1.0 and flattened to (T*N, ...); actions / weights padded
     with 0; tour masks padded with 1; episode masks 0 on the first row block only."""
     obs, prev, expert, w, tour = zip(*samples)
+    obs = [expand_once_records(o, p.size(0)) for o, p in zip(obs, prev)]  # (text features: one record per trajectory)
     T = max(p.size(0) for p in prev)
     batch_obs = {k: time_major([o[k] for o in obs], T, 1.0).flatten(0, 1) for k in obs[0]}
     expert_tn = time_major(expert, T, 0)

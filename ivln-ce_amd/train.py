@@ -212,7 +212,8 @@ def instruction_backward(ie, st, d_txt, rows, L, G):
     for d, (dgi, dgh, _) in enumerate(per_dir):  # (LSTM: one pre-activation sum, so one column sum serves both biases)
         G[bih[d]] = _colsum(dgi)
         G[bhh[d]] = G[bih[d]] if dgh is dgi else _colsum(dgh)
-    if ie.embedding_layer.weight.requires_grad:
+    # (pre-computed features, InstructionEncoder.uses_features: no embedding layer, and the features take no gradient)
+    if not ie.uses_features and ie.embedding_layer.weight.requires_grad:
         d_emb = ops.linear_bwd_input(per_dir[0][0], wih[0])
         if nd == 2:
             ops.linear_bwd_input(per_dir[1][0], wih[1], out=d_emb, accumulate=True)

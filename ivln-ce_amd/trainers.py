@@ -32,7 +32,8 @@ from .envs import construct_envs
 from .obs_transforms import apply_obs_transforms_batch, apply_obs_transforms_obs_space, get_active_obs_transforms
 from .registry import baseline_registry
 from .tour_ndtw import compute_tour_ndtw
-from .utils import (add_batched_data_to_observations, batch_obs, batch_to, dedupe_instructions,
+from .utils import (ONCE_KEYS, add_batched_data_to_observations, batch_obs, batch_to, dedupe_instruction_features,
+                    dedupe_instructions, expand_once_records,
                     extract_instruction_tokens, trim_instruction_padding)
 
 
@@ -322,8 +323,16 @@ class TrajectoryStore:
             if f.endswith(".npz") or f == "0.json":
                 os.remove(os.path.join(self.path, f))
 
+    # utils.ONCE_KEYS: kept ONCE per trajectory, as a (1, ...) record; every reader's collate step (collate_fn here,
+    # tour_batches.tour_collate) repeats it over the trajectory's timesteps through utils.expand_once_records
+    ONCE_KEYS = ONCE_KEYS
+
     def put(self, idx, traj_obs: Dict[str, np.ndarray], prev_actions, oracle_actions, tour_id=None):
         d = {"obs/" + k: v for k, v in traj_obs.items()}
+        for k in self.ONCE_KEYS:
+            v = d.get("obs/" + k)
+            if v is not None and v.shape[0] > 1 and all(np.array_equal(v[0], r, equal_nan=True) for r in v[1:]):
+                d["obs/" + k] = v[:1]
         d["prev_actions"] = np.asarray(prev_actions, np.int64)
         d["oracle_actions"] = np.asarray(oracle_actions, np.int64)
         if tour_id is not None:
@@ -369,6 +378,7 @@ def collate_fn(batch):
     prev, corr, weights = slab(first_prev, 0), slab(first_corr, 0), slab(first_w, 0)
     for col, (o, p, c, w) in enumerate(batch):
         L = lengths[col]
+        o = expand_once_records(o, L)
         for k, dst in obs.items():
             dst[:L, col] = o[k]
         prev[:L, col], corr[:L, col], weights[:L, col] = p, c, w
@@ -1015,6 +1025,7 @@ class PrefetchLoader:
                 for batch in self.loader:
                     # host side, before the H2D copy; batch[-2] = corrected actions (T, N)
                     obs_h = dedupe_instructions(trim_instruction_padding(batch[0], first_rows=batch[-2].shape[1]))
+                    obs_h = dedupe_instruction_features(obs_h, first_rows=batch[-2].shape[1])  # ("rxr_instruction" batches)
                     batch = (obs_h,) + tuple(batch[1:])
                     parts = tuple(pin(b) for b in batch)
                     if len(parts) == 5:  # episodic collate: no tour masks (slot 3 of the 6-tuple the loops unpack)
@@ -1235,9 +1246,18 @@ class DaggerTrainer(BaseVLNCETrainer):
     def _store_episode(self, episode, idx, expert_uuid):
         """`save_episode_to_disk` (iterative_collection_dagger_trainer.py:60-80, dagger_trainer.py:352-371): record
         `idx` = [obs{key: (T, ...)} without the expert sensor, prev_actions i64 (T,), oracle_actions i64 (T,)]."""
-        traj_obs = batch_obs([step[0] for step in episode], device=torch.device("cpu"))
+        steps = [step[0] for step in episode]
+        once = {}
+        for k in TrajectoryStore.ONCE_KEYS:  # (text features: never stacked over the timesteps, kept as one (1, L, E) record)
+            if k in steps[0]:
+                first = np.asarray(steps[0][k])
+                if all(s[k] is steps[0][k] or np.array_equal(first, np.asarray(s[k]), equal_nan=True) for s in steps[1:]):
+                    once[k] = first[None]
+                    steps = [{kk: vv for kk, vv in s.items() if kk != k} for s in steps]
+        traj_obs = batch_obs(steps, device=torch.device("cpu"))
         del traj_obs[expert_uuid]
         traj_obs = {k: v.numpy() for k, v in traj_obs.items() if torch.is_tensor(v)}
+        traj_obs.update(once)
         if self.config.IL.DAGGER.lmdb_fp16:
             traj_obs = {k: v.astype(np.float16) for k, v in traj_obs.items()}
         self.store.put(idx, traj_obs, [step[1] for step in episode], [step[2] for step in episode],

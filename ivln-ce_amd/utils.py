@@ -104,6 +104,52 @@ def dedupe_instructions(observations: Dict, key: str = "instruction") -> Dict:
     return observations
 
 
+# Observations that are the same at every timestep of a trajectory and large (pre-computed text features: 1.5 MB per
+# timestep): trainers.TrajectoryStore keeps them ONCE, as a (1, ...) record, and every collate step repeats them over the
+# trajectory's timesteps (`expand_once_records`).
+ONCE_KEYS = ("rxr_instruction",)
+
+
+def expand_once_records(obs: Dict, steps: int) -> Dict:
+    """A trajectory's observations as the store returns them -> every `ONCE_KEYS` entry held as a (1, ...) record becomes a
+    (steps, ...) view of it (no copy): what the collate steps pad and stack like any other observation."""
+    out = obs
+    for k in ONCE_KEYS:
+        v = obs.get(k)
+        if v is not None and v.shape[0] == 1 and steps > 1:
+            if out is obs:
+                out = dict(obs)
+            out[k] = v.expand(steps, *v.shape[1:])
+    return out
+
+
+def dedupe_instruction_features(observations: Dict, first_rows: int, key: str = "rxr_instruction") -> Dict:
+    """`dedupe_instructions` for pre-computed text features (INSTRUCTION_ENCODER.sensor_uuid "rxr_instruction"): a HOST-side
+    collated time-major (T*N, L, E) float batch, `first_rows` = N trajectories.  collate_fn repeats a trajectory's features
+    at every timestep and pads finished trajectories with 1.0 (dagger_trainer.py:66-70), so row (t, n) maps to n when it
+    equals row (0, n) bit for bit and to N when it is all ones; adds `<key>_unique` (N + 1, L, E) - the t = 0 rows and the
+    padding row - and `<key>_index` (T*N,), which the policies consume like the token pair.  The batch is left alone when
+    any row is neither (or it is on the device, or T < 2).  Two elementwise compares over the batch: no sort or
+    `torch.unique` over rows that are hundreds of thousands of floats wide."""
+    t = observations.get(key)
+    N = int(first_rows)
+    if (t is None or not torch.is_tensor(t) or t.is_cuda or t.dim() != 3 or t.dtype != torch.float32 or N < 1
+            or t.shape[0] % N != 0 or t.shape[0] < 2 * N):
+        return observations
+    T, L, E = t.shape[0] // N, t.shape[1], t.shape[2]
+    bits = t.contiguous().view(torch.int32).view(T, N, L * E)
+    same = (bits == bits[:1]).all(dim=2)                                              # (T, N): row (t, n) is row (0, n)
+    pad = (bits == torch.ones((), dtype=torch.float32).view(torch.int32)).all(dim=2)  # (T, N): collate_fn's padding row
+    if not bool((same | pad).all()):
+        return observations
+    index = torch.arange(N, dtype=torch.int32).expand(T, N).clone()
+    index[~same] = N
+    observations = dict(observations)
+    observations[key + "_unique"] = torch.cat([t[:N], torch.ones((1, L, E), dtype=torch.float32)], 0).contiguous()
+    observations[key + "_index"] = index.reshape(-1).contiguous()
+    return observations
+
+
 def add_batched_data_to_observations(observations: List[Dict], batched_data, batched_data_key: str):
     if batched_data is not None:
         for i in range(len(observations)):
