@@ -40,6 +40,14 @@ def _sig(L):
     L.ivln_mapper_known_raster.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.ivln_mapper_status.argtypes = [vp, C.POINTER(i64), vp]
     L.ivln_mapper_world_export.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64), vp]
+    # include/ivln_known_lib.h
+    L.ivln_known_lib_create.argtypes = [i32, C.POINTER(vp)]
+    L.ivln_known_lib_destroy.argtypes = [vp]
+    L.ivln_known_lib_add.argtypes = [vp, i32, vp, vp, i64, vp, vp]
+    L.ivln_known_lib_size.argtypes = [vp]
+    L.ivln_mapper_known_attach.argtypes = [vp, vp]
+    L.ivln_mapper_known_step.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.ivln_mapper_known_count.argtypes = [vp, i32, C.POINTER(i64), vp]
 
 
 def lib():

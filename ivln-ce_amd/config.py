@@ -240,6 +240,10 @@ def _experiment_defaults() -> Config:
     # capacity in points (0 = 2^20 per env); exceeding either raises through MappingModule.check_status()
     _C.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER.table_cells = 0
     _C.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER.world_capacity = 0
+    # known-map plugins (not a reference key): True = device-resident scene library, rows latch a scene index and the step
+    # can be captured (mapping.KnownSceneLibrary); False = the copy path (a scene's points are copied into the row's world
+    # cloud on every reset and the whole world is compacted every step; eager only)
+    _C.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER.known_library = True
     # --- MODEL (default.py:98-163) ---
     _C.MODEL = CN()
     _C.MODEL.policy_name = "CMAPolicy"

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <new>
 #include "../../include/ivln_hip.h"
+#include "../../include/ivln_known_lib.h"
 
 namespace {
 
@@ -613,7 +614,96 @@ __global__ void k_frames(const float* __restrict__ pose, const double* __restric
     frame_rot(orient, b, rot + 9 * b);
 }
 
+// ---- known-map mode over a scene library (include/ivln_known_lib.h): the cloud of a row is always one whole file, so
+// the device holds every scene once and a row holds the INDEX of its scene; nothing is copied per step or per reset and
+// no launch takes a host-side count ----
+struct KScene {  // 16-byte table entry, written by k_known_pack
+    const Pt* rec;  // records (x, y, z, label) in file order
+    int n;
+    int present;
+};
+constexpr int kKnownBlocks = 256;  // workgroups per row of the library raster (grid-stride over the scene)
+
+__global__ __launch_bounds__(kThreads) void k_known_pack(const float* __restrict__ xyz, const uint8_t* __restrict__ semv,
+                                                         int n, Pt* __restrict__ rec, KScene* entry) {
+    for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i < (unsigned)n; i += gridDim.x * kThreads) {
+        Pt q;
+        q.x = xyz[3 * (size_t)i]; q.y = xyz[3 * (size_t)i + 1]; q.z = xyz[3 * (size_t)i + 2];
+        q.meta = semv[i];
+        rec[i] = q;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // (read by launches BEHIND this one on the stream)
+        entry->rec = rec;
+        entry->n = n;
+        entry->present = 1;
+    }
+}
+
+__device__ __forceinline__ bool known_scene_ok(int c, const KScene* __restrict__ table, int n_scenes) {
+    return c >= 0 && c < n_scenes && table[c].present != 0;
+}
+
+// latch + rotation (workgroup 0, one thread per row of the handle) and the zeroing of the occupancy output (all)
+__global__ __launch_bounds__(kThreads) void k_known_latch(const int32_t* __restrict__ scene_id,
+                                                          const uint8_t* __restrict__ not_done,
+                                                          const double* __restrict__ orient, int B, int B_max,
+                                                          int* __restrict__ cur, float* __restrict__ rot,
+                                                          const KScene* __restrict__ table, int n_scenes, Scalars* sc,
+                                                          uint8_t* __restrict__ occ, int map_cells) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < map_cells) occ[i] = 0;
+    if (blockIdx.x == 0 && (int)threadIdx.x < B_max) {
+        const int b = threadIdx.x;
+        int c = -1;  // a row at or above the batch size is cleared (mapper.py:315-318)
+        if (b < B) {
+            c = not_done[b] == 0 ? scene_id[b] : cur[b];  // cleared and reloaded in the same step (mapper.py:851-881)
+            frame_rot(orient, b, rot + 9 * b);
+        }
+        cur[b] = c;
+        if (c != -1 && !known_scene_ok(c, table, n_scenes)) sc->err = IVLN_E_INVALID;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_known_lib_raster(const int* __restrict__ cur, const KScene* __restrict__ table,
+                                                               int n_scenes, const float* __restrict__ pose,
+                                                               const float* __restrict__ rot, int rows, int cols, float res,
+                                                               float half_h, float half_w, uint8_t* __restrict__ occ,
+                                                               unsigned long long* __restrict__ cell) {
+    const int b = blockIdx.y;  // wave-uniform: the row's latch, table entry, pose and rotation are scalar loads
+    const int c = cur[b];
+    if (!known_scene_ok(c, table, n_scenes)) return;  // -1: never reset; anything else was reported by k_known_latch
+    // (16-byte aligned: ivln_known_lib_add.  A pointer read from memory is generic to the compiler; the records are global
+    //  memory, and saying so makes the load a global one instead of a flat one)
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4* GlobalRec;
+    const GlobalRec rec = (GlobalRec)(uintptr_t)table[c].rec;
+    const unsigned n = (unsigned)table[c].n;  // < 2^31: i + stride cannot wrap
+    for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const u32x4 v = rec[i];  // one 16-byte load per point
+        Pt p;
+        p.x = __uint_as_float(v.x); p.y = __uint_as_float(v.y); p.z = __uint_as_float(v.z);
+        p.meta = ((uint32_t)b << 8) | (v.w & 0xFFu);
+        raster_point(p, (uint64_t)i, pose, rot, rows, cols, res, half_h, half_w, occ, cell);
+    }
+}
+
+__global__ void k_known_count(const int* __restrict__ cur, const KScene* __restrict__ table, int n_scenes, int B,
+                              long long* __restrict__ out) {
+    long long s = 0;
+    for (int b = 0; b < B; ++b) {
+        const int c = cur[b];
+        if (known_scene_ok(c, table, n_scenes)) s += table[c].n;
+    }
+    *out = s;
+}
+
 }  // namespace
+
+struct ivln_known_lib {
+    int max_scenes, n_added;
+    KScene* table;  // device, fixed for the life of the library
+    uint8_t* added;  // host: scene indices that have an entry
+};
 
 struct ivln_mapper {
     int B_max, H, W, rows, cols;
@@ -631,6 +721,11 @@ struct ivln_mapper {
     int n_blocks_local;
     int local_blocks, world_blocks;  // launch width of the local- / world-cloud kernels (0: full width)
     int64_t known_rank;
+    // library-mode known steps (include/ivln_known_lib.h); allocated by ivln_mapper_known_attach
+    const ivln_known_lib* klib;
+    int* kcur;          // latched scene index per row (-1: none)
+    float* krot;        // ego rotation per row, derived by the step's first launch
+    long long* kcount;  // result word of ivln_mapper_known_count
 };
 
 #define HIPCHK(x)                          \
@@ -687,6 +782,7 @@ int ivln_mapper_create(int B_max, int H, int W, double vfov_rad, double height_m
     m->table_cells = table_cells > 0 ? table_cells : (int64_t)(16 << 20);
     if (m->table_cells > (1ll << 31)) m->table_cells = 1ll << 31;  // ranks = keys must fit 31 bits (k_world_max)
     m->known_rank = 0;
+    m->klib = nullptr; m->kcur = nullptr; m->krot = nullptr; m->kcount = nullptr;
     m->local_blocks = m->world_blocks = 0;
     // core.py:70-115: intrinsics in python doubles -> fp32; (u + 0.5 - cx) / fx in fp32
     double hfov = (double)W / (double)H * vfov_rad;
@@ -741,6 +837,9 @@ int ivln_mapper_destroy(ivln_mapper* m) {
     (void)hipFree(m->wbuf[0]); (void)hipFree(m->wbuf[1]); (void)hipFree(m->rbuf[0]); (void)hipFree(m->rbuf[1]);
     (void)hipFree(m->tab64); (void)hipFree(m->cell); (void)hipFree(m->sc); (void)hipFree(m->bmmL); (void)hipFree(m->bmmA);
     (void)hipFree(m->bbox);
+    if (m->kcur) (void)hipFree(m->kcur);
+    if (m->krot) (void)hipFree(m->krot);
+    if (m->kcount) (void)hipFree(m->kcount);
     delete m;
     return IVLN_OK;
 }
@@ -748,6 +847,7 @@ int ivln_mapper_destroy(ivln_mapper* m) {
 int ivln_mapper_reset(ivln_mapper* m, void* stream) {
     if (!m) return IVLN_E_INVALID;
     m->known_rank = 0;
+    if (m->kcur) HIPCHK(hipMemsetAsync(m->kcur, 0xFF, sizeof(int) * (size_t)m->B_max, (hipStream_t)stream));  // -1: no scene
     return init_scalars(m, (hipStream_t)stream);
 }
 
@@ -890,6 +990,97 @@ int ivln_mapper_known_raster(ivln_mapper* m, const float* pose, const float* rot
     hipLaunchKernelGGL(k_finalize, dim3((map_cells + kThreads - 1) / kThreads), dim3(kThreads), 0, s, m->cell,
                        sem_out, map_cells, m->sc, 0, (unsigned)m->capacity, 0, 0);
     return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+}
+
+// ---- known-map mode over a scene library (include/ivln_known_lib.h) ----
+int ivln_known_lib_create(int max_scenes, ivln_known_lib** out) {
+    if (!out || max_scenes <= 0 || max_scenes > (1 << 20)) return IVLN_E_INVALID;
+    ivln_known_lib* lib = new (std::nothrow) ivln_known_lib();
+    if (!lib) return IVLN_E_INVALID;
+    lib->max_scenes = max_scenes;
+    lib->n_added = 0;
+    lib->table = nullptr;
+    lib->added = (uint8_t*)calloc((size_t)max_scenes, 1);
+    if (!lib->added || hipMalloc(&lib->table, sizeof(KScene) * (size_t)max_scenes) != hipSuccess ||
+        hipMemset(lib->table, 0, sizeof(KScene) * (size_t)max_scenes) != hipSuccess) {
+        ivln_known_lib_destroy(lib);
+        return IVLN_E_HIP;
+    }
+    *out = lib;
+    return IVLN_OK;
+}
+
+int ivln_known_lib_destroy(ivln_known_lib* lib) {
+    if (!lib) return IVLN_OK;
+    if (lib->table) (void)hipFree(lib->table);
+    free(lib->added);
+    delete lib;
+    return IVLN_OK;
+}
+
+int ivln_known_lib_add(ivln_known_lib* lib, int scene, const float* xyz, const uint8_t* sem, int64_t n, void* records,
+                       void* stream) {
+    if (!lib || scene < 0 || scene >= lib->max_scenes || lib->added[scene] || n < 0 || n >= (1ll << 31)) return IVLN_E_INVALID;
+    if (n > 0 && (!xyz || !sem || !records || ((uintptr_t)records & 15u))) return IVLN_E_INVALID;
+    int blocks = (int)((n + kThreads - 1) / kThreads);
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;  // (an empty scene still gets its entry)
+    hipLaunchKernelGGL(k_known_pack, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, xyz, sem, (int)n, (Pt*)records,
+                       lib->table + scene);
+    if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
+    lib->added[scene] = 1;
+    lib->n_added += 1;
+    return IVLN_OK;
+}
+
+int ivln_known_lib_size(ivln_known_lib* lib) { return lib ? lib->n_added : IVLN_E_INVALID; }
+
+int ivln_mapper_known_attach(ivln_mapper* m, ivln_known_lib* lib) {
+    if (!m || !lib) return IVLN_E_INVALID;
+    if (!m->kcur) {
+        int* cur = nullptr;
+        float* rot = nullptr;
+        long long* cnt = nullptr;
+        const bool ok = hipMalloc(&cur, sizeof(int) * (size_t)m->B_max) == hipSuccess &&
+                        hipMalloc(&rot, sizeof(float) * 9 * (size_t)m->B_max) == hipSuccess &&
+                        hipMalloc(&cnt, sizeof(long long)) == hipSuccess &&
+                        hipMemset(cur, 0xFF, sizeof(int) * (size_t)m->B_max) == hipSuccess &&
+                        hipMemset(rot, 0, sizeof(float) * 9 * (size_t)m->B_max) == hipSuccess;
+        if (!ok) {
+            (void)hipFree(cur); (void)hipFree(rot); (void)hipFree(cnt);
+            return IVLN_E_HIP;
+        }
+        m->kcur = cur; m->krot = rot; m->kcount = cnt;
+    }
+    m->klib = lib;
+    return IVLN_OK;
+}
+
+int ivln_mapper_known_step(ivln_mapper* m, const int32_t* scene_id, const float* pose, const double* orientation,
+                           const uint8_t* not_done, int B, uint8_t* occ_out, uint8_t* sem_out, void* stream) {
+    if (!m || !m->klib || !scene_id || !pose || !orientation || !not_done || !occ_out || !sem_out || B <= 0 || B > m->B_max)
+        return IVLN_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int map_cells = B * m->rows * m->cols;
+    const int cell_blocks = (map_cells + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(k_known_latch, dim3(cell_blocks), dim3(kThreads), 0, s, scene_id, not_done, orientation, B, m->B_max,
+                       m->kcur, m->krot, m->klib->table, m->klib->max_scenes, m->sc, occ_out, map_cells);
+    hipLaunchKernelGGL(k_known_lib_raster, dim3(kKnownBlocks, B), dim3(kThreads), 0, s, m->kcur, m->klib->table,
+                       m->klib->max_scenes, pose, m->krot, m->rows, m->cols, m->res, m->half_h, m->half_w, occ_out, m->cell);
+    hipLaunchKernelGGL(k_finalize, dim3(cell_blocks), dim3(kThreads), 0, s, m->cell, sem_out, map_cells, m->sc, 0,
+                       (unsigned)m->capacity, 0, 0);
+    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+}
+
+int ivln_mapper_known_count(ivln_mapper* m, int B, int64_t* n, void* stream) {
+    if (!m || !m->klib || !n || B <= 0 || B > m->B_max) return IVLN_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_known_count, dim3(1), dim3(1), 0, s, m->kcur, m->klib->table, m->klib->max_scenes, B, m->kcount);
+    long long h = 0;
+    HIPCHK(hipMemcpyAsync(&h, m->kcount, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n = (int64_t)h;
+    return IVLN_OK;
 }
 
 int ivln_mapper_status(ivln_mapper* m, int64_t* world_n, void* stream) {

@@ -134,6 +134,7 @@ class GraphedRollout:
         if streams == "split" and not self._staged:
             raise TypeError(f"streams='split' needs MapCMANet's stages; {type(policy.net).__name__} has none")
         self.transforms = list(obs_transforms)
+        self._host_staged = [t for t in self.transforms if hasattr(t, "stage_host")]
         self._warmup_mapper = warmup_mapper
         self.deterministic = deterministic
         dev = next(policy.parameters()).device
@@ -157,6 +158,7 @@ class GraphedRollout:
         # the fused head's scratch is baked into the captured graphs: this runner owns one (ops.cma_step_ws)
         prev_owner, ops.CMA_WS_OWNER = ops.CMA_WS_OWNER, id(self)
         try:
+            self._stage_host()  # (the host's part of the warm-up steps and of the capture, which executes nothing)
             if hasattr(policy.net, "prepare_capture"):
                 policy.net.prepare_capture(self.static)
             if self.split:
@@ -471,6 +473,14 @@ class GraphedRollout:
             self.graphs.append(g)
         self.phase = 0
 
+    def _stage_host(self):
+        """The part of the step that needs the host, outside the captured region and in front of it on the current stream:
+        `stage_host(observations)` of every transformer that has one (library-mode known mappers: scene names -> indices,
+        loading of an unseen scene, one async copy), with the step's observations - `load` has put the non-tensor entries
+        (env_name) into `static`."""
+        for t in self._host_staged:
+            t.stage_host(self.static)
+
     def load(self, obs: Dict):
         """Observation tensors -> the captured input buffers: one multi-copy launch for everything that is
         already a matching contiguous device tensor, Tensor.copy_ (H2D / cast / strided) for the rest."""
@@ -494,6 +504,8 @@ class GraphedRollout:
         Returns the (B,1) int64 action tensor (one of the two persistent buffers)."""
         if obs is not None:
             self.load(obs)
+        if self._host_staged:
+            self._stage_host()
         if self.split:
             self._replay_split()
         else:

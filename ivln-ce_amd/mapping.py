@@ -77,13 +77,95 @@ class OccupancySemanticMapMemory:
         return self._sem[: self.batch_size]
 
 
+def load_known_scene(maps_location, env_name):
+    """{maps_location}/{env_name}.npz -> (xyz (n, 3) float32, semantics (n,) uint8), contiguous numpy arrays in file order
+    (mapper.py:283-294)."""
+    with np.load(os.path.join(maps_location, f"{env_name}.npz")) as f:
+        xyz = np.ascontiguousarray(f["xyz"], dtype=np.float32).reshape(-1, 3)
+        sem = np.ascontiguousarray(f["semantics"]).astype(np.int64).astype(np.uint8).reshape(-1)
+    return xyz, sem
+
+
+class KnownSceneLibrary:
+    """Device-resident scene clouds of known-map mode, each held once (include/ivln_known_lib.h).  The host side is a
+    dict name -> index; a scene is read from `{maps_location}/{name}.npz` the first time its name is seen, packed on the
+    device into 16-byte records (x, y, z, label) and entered into the library's device table, whose address never changes -
+    a captured step that is replayed behind an `index()` call sees the new scene.  The record tensors live as long as
+    the library does."""
+
+    def __init__(self, device, maps_location, max_scenes: int = 1024):
+        self.device = device
+        self.maps_location = maps_location
+        self.max_scenes = int(max_scenes)
+        self._index: Dict[str, int] = {}
+        self._records: List[torch.Tensor] = []
+        self._h = None
+
+    def __len__(self):
+        return len(self._index)
+
+    def __contains__(self, name):
+        return name in self._index
+
+    def names(self):
+        return list(self._index)
+
+    def points(self, name) -> int:
+        return int(self._records[self._index[name]].shape[0])
+
+    def handle(self):
+        """The C handle (created on first use, on the library's device)."""
+        if self._h is None:
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                check(lib().ivln_known_lib_create(self.max_scenes, C.byref(h)), "ivln_known_lib_create")
+            self._h = h
+        return self._h
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                lib().ivln_known_lib_destroy(self._h)
+                self._h = None
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _load(self, name):
+        xyz, sem = load_known_scene(self.maps_location, name)
+        return torch.from_numpy(xyz).to(self.device), torch.from_numpy(sem).to(self.device)
+
+    def _add(self, scene, xyz, sem, records):
+        """The C call (tests replace it with a stub): pack + table entry, one launch on the current stream."""
+        check(lib().ivln_known_lib_add(self.handle(), scene, xyz.data_ptr(), sem.data_ptr(), xyz.shape[0],
+                                       records.data_ptr(), stream_ptr()), "ivln_known_lib_add")
+
+    def index(self, name) -> int:
+        """Index of scene `name`; loads and adds it on first sight (host file read + one launch on the current stream)."""
+        i = self._index.get(name)
+        if i is None:
+            i = len(self._index)
+            if i >= self.max_scenes:
+                raise _lib.IvlnError(f"known-scene library is full ({self.max_scenes} scenes)")
+            xyz, sem = self._load(name)
+            records = torch.empty((xyz.shape[0], 4), dtype=torch.float32, device=self.device)
+            # (xyz / sem are read by a launch on the current stream, which is also the stream their memory returns to)
+            self._add(i, xyz.contiguous(), sem.contiguous(), records)
+            self._records.append(records)
+            self._index[name] = i
+        return i
+
+
 class MappingModule:
     """Drop-in for mapper.py:904-944 (`create_*_mapper` factories :950-1028).
 
     mode "iterative": labels come from `semantic12` (gt) or from `semantics_module(observations)`
     (predicted, e.g. RedNet) and the world cloud is built online.
     mode "known": the world cloud of each env is loaded from `{maps_location}/{env_name}.npz`
-    when its episode resets (mapper.py:851-881).
+    when its episode resets (mapper.py:851-881).  With `known_library=True` the scenes live once in a
+    `KnownSceneLibrary` and a row only latches the index of its scene (ivln_mapper_known_step): no per-step copy, no
+    host read inside the step - `stage_host` does the host's part in front of it - so the step can be captured.  Every
+    step of such a module goes through the library; without the flag the copy path (ivln_mapper_known_begin /
+    _load_known / _known_raster) runs as before.
     """
 
     def __init__(
@@ -97,6 +179,7 @@ class MappingModule:
         b_max: int = 64,
         world_capacity: int = 0,
         table_cells: int = 0,
+        known_library: bool = False,
     ):
         if device.type != "cuda":
             raise _lib.IvlnError("the HIP mapper needs a GPU device (no CPU fallback)")
@@ -117,6 +200,14 @@ class MappingModule:
         self._T = torch.empty((b_max, 4, 4), dtype=torch.float32, device=device)
         self._rot = torch.empty((b_max, 3, 3), dtype=torch.float32, device=device)
         self._known_cache: Dict[str, tuple] = {}
+        self.known_library = bool(known_library) and mode == "known"
+        if self.known_library:
+            self.scene_library = KnownSceneLibrary(device, maps_location)
+            self._scene_dev = torch.full((b_max,), -1, dtype=torch.int32, device=device)  # the step's scene index per row
+            # pinned staging rows, used in turn: a row is rewritten only after the copy that read it has run
+            self._scene_pin = [torch.zeros((b_max,), dtype=torch.int32).pin_memory() for _ in range(4)]
+            self._scene_ev = [None] * 4
+            self._scene_turn = 0
 
     # -- handle management ---------------------------------------------------------------
     def _ensure_handle(self, H, W):
@@ -136,6 +227,8 @@ class MappingModule:
                 "ivln_mapper_create",
             )
         self._h, self._hw = h, (H, W)
+        if self.known_library:
+            check(lib().ivln_mapper_known_attach(self._h, self.scene_library.handle()), "ivln_mapper_known_attach")
         if getattr(self, "_width", (0, 0)) != (0, 0):
             check(lib().ivln_mapper_set_launch_width(self._h, *self._width), "ivln_mapper_set_launch_width")
 
@@ -164,6 +257,29 @@ class MappingModule:
         )
         return self._T[:B], self._rot[:B], pose
 
+    # -- library-mode known maps: the host's part of a step ------------------------------------------
+    def stage_host(self, observations):
+        """Everything a library-mode step needs from the host, in front of the step (graphed.GraphedRollout calls it before
+        each replay): scene names -> indices (an unseen scene is read and added to the library here) and ONE async copy of
+        the indices from pinned memory into the persistent device buffer the step reads.  No device-to-host traffic."""
+        if not self.known_library:
+            return
+        names = observations["env_name"]
+        B = len(names)
+        if B > self.b_max:
+            raise _lib.IvlnError(f"batch {B} > b_max {self.b_max}")
+        k = self._scene_turn
+        self._scene_turn = (k + 1) % len(self._scene_pin)
+        if self._scene_ev[k] is not None:
+            self._scene_ev[k].synchronize()
+        pin = self._scene_pin[k]
+        index = self.scene_library.index
+        pin.numpy()[:B] = [index(name) for name in names]
+        self._scene_dev[:B].copy_(pin[:B], non_blocking=True)
+        ev = self._scene_ev[k] or torch.cuda.Event()
+        ev.record()
+        self._scene_ev[k] = ev
+
     # -- one step -----------------------------------------------------------------------------
     def forward(self, observations: Dict[str, torch.Tensor], T=None, rot=None) -> OccupancySemanticMapMemory:
         """observations: the dict the reference's `Mapper.forward` receives
@@ -177,8 +293,9 @@ class MappingModule:
         self._ensure_handle(H, W)
         depth = depth.to(torch.float32).contiguous()
         not_done = observations["not_done_masks"].reshape(-1).to(torch.uint8).contiguous()
-        posed = T is None and self.mode == "iterative" and STEP_POSED
-        if posed:  # the transforms are derived inside the step's first kernel (ivln_mapper_step_posed)
+        posed = (T is None and self.mode == "iterative" and STEP_POSED) or self.known_library
+        if posed:  # (library-mode known steps derive their rotation the same way: ivln_mapper_known_step)
+            # the transforms are derived inside the step's first kernel (ivln_mapper_step_posed)
             pose = observations["world_robot_pose"].to(self.device, torch.float32).contiguous()
             orientation = observations["world_robot_orientation"].to(self.device, torch.float64).contiguous()
         elif T is None:
@@ -219,6 +336,16 @@ class MappingModule:
                     ),
                     "ivln_mapper_step",
                 )
+        elif self.known_library:
+            if not torch.cuda.is_current_stream_capturing():  # (a captured step: the runner staged in front of the replay)
+                self.stage_host(observations)
+            if getattr(self, "dry_run", False):
+                return mem
+            check(
+                lib().ivln_mapper_known_step(self._h, dptr(self._scene_dev), dptr(pose), dptr(orientation), dptr(not_done),
+                                             B, dptr(mem._occ), dptr(mem._sem), s),
+                "ivln_mapper_known_step",
+            )
         else:
             check(lib().ivln_mapper_known_begin(self._h, dptr(not_done), B, s), "ivln_mapper_known_begin")
             finished = (not_done == 0).nonzero().reshape(-1).tolist()
@@ -286,16 +413,17 @@ class MappingModule:
 
     def _load_known(self, env_name):
         if env_name not in self._known_cache:
-            with np.load(os.path.join(self.maps_location, f"{env_name}.npz")) as f:  # mapper.py:283-294
-                xyz = torch.from_numpy(np.ascontiguousarray(f["xyz"], dtype=np.float32)).to(self.device)
-                sem = torch.from_numpy(np.ascontiguousarray(f["semantics"]).astype(np.int64).astype(np.uint8)).to(self.device)
-            self._known_cache[env_name] = (xyz.contiguous(), sem.contiguous())
+            xyz, sem = load_known_scene(self.maps_location, env_name)
+            self._known_cache[env_name] = (torch.from_numpy(xyz).to(self.device), torch.from_numpy(sem).to(self.device))
         return self._known_cache[env_name]
 
     # -- introspection (tests) -----------------------------------------------------------------
     def status(self):
         n = C.c_int64(0)
         code = lib().ivln_mapper_status(self._h, C.byref(n), stream_ptr())
+        if self.known_library:  # the world size the copy path would report: the latched scenes of the current batch rows
+            check(lib().ivln_mapper_known_count(self._h, self.map_memory.batch_size, C.byref(n), stream_ptr()),
+                  "ivln_mapper_known_count")
         return code, n.value
 
     def set_launch_width(self, local_blocks: int = 0, world_blocks: int = 0):

@@ -129,6 +129,7 @@ class Mapper(ObservationTransformer):
         mp = config.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER
         tr.sizing = {k: int(getattr(mp, k)) for k in ("table_cells", "world_capacity") if int(getattr(mp, k, 0) or 0) > 0}
         tr.sizing["b_max"] = 64  # envs per process the mapper is sized for (ivln_mapper_create: <= 64)
+        tr.known_library = bool(getattr(mp, "known_library", True))  # (read by the known-map plugins only)
         return tr
 
 
@@ -158,22 +159,36 @@ class PredictedSemanticsIterativeMapper(Mapper):
             )
 
 
-@baseline_registry.register_obs_transformer()
-class GTSemanticsKnownMapper(Mapper):
+class _KnownMapper(Mapper):
+    """Known-map plugins.  Built by `from_config` they run in library mode unless EGOCENTRIC_MAPPER.known_library is False
+    (mapping.MappingModule, known_library=True): the step is then device work only and `stage_host` is the host's part of
+    it, which a replaying runner calls in front of every replay (graphed.GraphedRollout); an eager `forward` stages for
+    itself.  Built through the reference's constructor signature they keep the copy path."""
+
+    known_library = False
+    _factory = None
+
     def setup_mapping_module(self, observations):
         if self.mapping_module is None:
-            self.mapping_module = create_gt_semantics_known_mapper(
-                device=observations["depth"].device, map_dimensions=self.map_dimensions, **self.sizing
+            self.mapping_module = type(self)._factory(
+                device=observations["depth"].device, map_dimensions=self.map_dimensions,
+                known_library=self.known_library, **self.sizing
             )
+
+    def stage_host(self, observations):
+        """Host work of the coming step: scene names -> library indices (an unseen scene is loaded), one async copy."""
+        self.setup_mapping_module(observations)
+        self.mapping_module.stage_host(observations)
 
 
 @baseline_registry.register_obs_transformer()
-class PredictedSemanticsKnownMapper(Mapper):
-    def setup_mapping_module(self, observations):
-        if self.mapping_module is None:
-            self.mapping_module = create_predicted_semantics_known_mapper(
-                device=observations["depth"].device, map_dimensions=self.map_dimensions, **self.sizing
-            )
+class GTSemanticsKnownMapper(_KnownMapper):
+    _factory = staticmethod(create_gt_semantics_known_mapper)
+
+
+@baseline_registry.register_obs_transformer()
+class PredictedSemanticsKnownMapper(_KnownMapper):
+    _factory = staticmethod(create_predicted_semantics_known_mapper)
 
 
 def get_active_obs_transforms(config):

@@ -586,8 +586,10 @@ class BaseVLNCETrainer:
 
     def _graph_eligible(self, sampled=False):
         """The step can be captured when actions are deterministic - or sampled on the device from host uniforms
-        (`sampled`: the collection loops, see _RolloutStepper) - and every transformer is an iterative mapper (the
-        known-map ones read files on episode reset: host work that cannot live in a graph)."""
+        (`sampled`: the collection loops, see _RolloutStepper) - and every transformer is an iterative mapper or a known-map
+        one in library mode (`known_library`, the default of the plugins: scenes are device-resident and the file reads of
+        an episode reset happen in `stage_host`, which the runner calls in front of each replay; the copy path of a
+        known mapper without the flag reads the device and files inside the step and stays eager)."""
         cfg = self.config
         if self.device.type != "cuda":
             return False
@@ -595,7 +597,9 @@ class BaseVLNCETrainer:
             return False
         if len(cfg.VIDEO_OPTION) > 0:  # the *_viz frames are host-side numpy (a D2H copy per step)
             return False
-        if not all(type(t).__name__.endswith("IterativeMapper") for t in self.obs_transforms):
+        if not all(type(t).__name__.endswith("IterativeMapper")
+                   or (type(t).__name__.endswith("KnownMapper") and getattr(t, "known_library", False))
+                   for t in self.obs_transforms):
             return False
         # MapCMA needs its mapper in the step; the map-free policies (Latent-CMA) are captured as they are
         return len(self.obs_transforms) > 0 or cfg.MODEL.policy_name != "MapCMAPolicy"
