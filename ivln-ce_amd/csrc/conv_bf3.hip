@@ -1186,8 +1186,9 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
 #endif
 }
 
-// Eligibility of the 1x1 kernels in their two forms.  mode: 0 = heuristic, 1 = insist
-int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin = -1) {
+// Eligibility of the 1x1 kernels in their two forms.  mode: 0 = heuristic, 1 = insist; *kind: the form launched, as
+// ivln_conv_split_kinds counts it (2 = K split over the waves, 3 = wave tiles)
+int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin, int* kind) {
     if (d.stride != 1 || d.pad != 0 || d.Cin % CB != 0 || d.Cin < 4 * CB || d.stat_partials || d.splits > 1) return IVLN_E_UNSUPPORTED;
     if ((d.HoWo & 3) || (d.in_img_stride & 3) || ((((uintptr_t)d.B) | ((uintptr_t)d.D) | ((uintptr_t)d.residual)) & 15)) return IVLN_E_UNSUPPORTED;
     const int64_t nimg = d.N / d.HoWo;
@@ -1220,6 +1221,7 @@ int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin =
         if (wt && wgs < ivln_cu_count()) return IVLN_E_UNSUPPORTED;  // (too few wave tiles to fill the chip: the tiled GEMMs split K)
     }
     d.splits = 1;
+    *kind = wt ? 3 : 2;
     const unsigned char* a = (const unsigned char*)d.A_split;
     const long long gb = (long long)(d.a_split_grp_stride * 4);
     if (wt) {
@@ -1909,8 +1911,9 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
             d.Wout != d.Win || d.K != d.Cin || d.HoWo != d.Hout * d.Wout || d.N % d.HoWo != 0)
             return IVLN_E_UNSUPPORTED;
         const int ovu = d.tile_override;
-        const int rc = bf3_1x1_ks_launch(d, s, (force || ovu == 11 || ovu == 12 || ovu == 13) ? 1 : 0, ovu == 12 ? 0 : (ovu == 13 ? 1 : -1));
-        return done(rc, flops, d.Cin / CB <= 16 ? 3 : 2, -1);
+        int kind1 = 2;  // (the form the launcher took: a pinned form or 24 / 32 / 48 chunks over many pixels is not the chunk count's)
+        const int rc = bf3_1x1_ks_launch(d, s, (force || ovu == 11 || ovu == 12 || ovu == 13) ? 1 : 0, ovu == 12 ? 0 : (ovu == 13 ? 1 : -1), &kind1);
+        return done(rc, flops, kind1, -1);
     }
     if (KS == 2) {
         // (the stacked classes multiply their common window's zero padding too: ivln_gemm_desc.real_taps)
@@ -1951,8 +1954,9 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     const bool ins1 = ov == 11 || ov == 12 || ov == 13 || post, ins3 = ov == 10 || ov == 14 || ov == 15;
     if (KS == 1 && ov < 20 && (ks1_env != 0 || ins1) && d.splits <= 1 && !d.defer_epilogue && d.HoWo == d.Hout * d.Wout &&
         d.K == d.Cin && d.N % d.HoWo == 0 && d.Hout == d.Hin && d.Wout == d.Win) {
-        const int rc = bf3_1x1_ks_launch(d, s, (ks1_env == 1 || ins1) ? 1 : 0, ov == 12 ? 0 : (ov == 13 ? 1 : -1));
-        if (rc != IVLN_E_UNSUPPORTED || ins1) return done(rc, flops, ov == 13 ? 3 : (ov == 12 ? 2 : (d.Cin / CB <= 16 ? 3 : 2)), 0);
+        int kind1 = 2;
+        const int rc = bf3_1x1_ks_launch(d, s, (ks1_env == 1 || ins1) ? 1 : 0, ov == 12 ? 0 : (ov == 13 ? 1 : -1), &kind1);
+        if (rc != IVLN_E_UNSUPPORTED || ins1) return done(rc, flops, kind1, 0);
     }
     if (ins1 || (ins3 && KS != 3)) return IVLN_E_UNSUPPORTED;
     if (KS == 1) {  // 1x1, stride 1 or 2, no padding

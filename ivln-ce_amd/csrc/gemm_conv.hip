@@ -444,6 +444,7 @@ constexpr int kFamilyCount = (int)(sizeof(kFamilyKernels) / sizeof(kFamilyKernel
 std::vector<hipEvent_t> g_timing_events;
 std::vector<int> g_timing_kernel;  // per timed launch: index into kFamilyKernels, kFamilyCount = a name outside the list
 int g_timing_used = -1;            // -1: not armed
+size_t g_timing_cap = 0;           // events this arming may use (2 per launch): the pool keeps the largest arming's events
 int g_timing_dropped = 0;
 double g_report_ms[kFamilyCount + 1];
 int g_report_n[kFamilyCount + 1];
@@ -461,7 +462,7 @@ int family_index(const char* site) {  // "(k_conv_direct<3, 32, ...>)" / "k_dept
 
 bool ivln_family_timing_next(hipEvent_t* start, hipEvent_t* stop, const char* kernel) {
     if (g_timing_used < 0) return false;
-    if ((size_t)g_timing_used + 2 > g_timing_events.size()) {
+    if ((size_t)g_timing_used + 2 > g_timing_cap) {
         ++g_timing_dropped;
         return false;
     }
@@ -487,6 +488,7 @@ extern "C" int ivln_family_timing_begin(int max_launches) {
         g_timing_events.push_back(e);
     }
     g_timing_kernel.assign(g_timing_events.size() / 2, kFamilyCount);
+    g_timing_cap = (size_t)max_launches * 2;  // (not the pool's size: an earlier, larger arming must not raise this one's limit)
     g_timing_used = 0;
     g_timing_dropped = 0;
     g_report_valid = false;
