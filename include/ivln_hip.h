@@ -173,7 +173,9 @@ typedef struct ivln_gemm_desc {
     int tile_override;
     /* optional (stride-1 3x3 / 7x7 / 2x2 convs): the weights pre-arranged by ivln_conv_pack_weights_f32; when set and
      * the direct kernel is chosen, its weight staging becomes a linear float4 copy.  A must still be given.
-     * 1x1 convs with K = 64 / 128 / 256 (KS = 1 in the pack call): the streaming kernel's per-lane register image. */
+     * 1x1 convs with K = 64 / 128 / 256 (KS = 1 in the pack call): the streaming kernel's per-lane register image.
+     * Either way the kernels read exactly the ivln_conv_packed_floats(M, Cin, KS) floats of a weight set, nothing behind them
+     * (K = 64 runs two 32-row tiles per wave: a second tile past the pack's last one re-reads the last). */
     const float* A_packed;
     /* 0 (default): workgroup ids are remapped so that each XCD (hardware places workgroup b on XCD b % 8, each
      * with its own 4 MB L2) works on one contiguous range of output tiles - neighbouring tiles share operand rows /

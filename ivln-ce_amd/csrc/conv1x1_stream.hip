@@ -36,11 +36,16 @@ __global__ __launch_bounds__(256) void k_conv1x1_stream(const ivln_gemm_desc p) 
     // ---- this wave's weights: a[mt][q] = W[m_base + 32 mt + l31][2 q + half] (rows past M repeat the last row; masked at the store) ----
     float a[MT][NQ];
     if (p.A_packed) {  // the per-lane register image (ivln_conv_pack_weights_f32, KS = 1): one coalesced 256-byte row per step
-        const float* __restrict__ ap = p.A_packed + (int64_t)grp * p.a_packed_grp_stride + (int64_t)(m_base >> 5) * NQ * 64 + lane;
+        // (the pack holds ceil(M / 32) row tiles: a wave's row tile past the last one - MT = 2 with an odd tile count - re-reads
+        //  the last tile, as the unpacked path clamps its row; those rows are masked at the store)
+        const float* __restrict__ ap = p.A_packed + (int64_t)grp * p.a_packed_grp_stride + lane;
+        const int last_tile = (p.M + 31) / 32 - 1;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+        for (int mt = 0; mt < MT; ++mt) {
+            const int tile = MT > 1 ? min((m_base >> 5) + mt, last_tile) : (m_base >> 5) + mt;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) a[mt][q] = ap[(mt * NQ + q) * 64];
+            for (int q = 0; q < NQ; ++q) a[mt][q] = ap[((int64_t)tile * NQ + q) * 64];
+        }
     } else {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {

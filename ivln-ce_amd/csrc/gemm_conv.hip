@@ -621,7 +621,8 @@ extern "C" int ivln_gemm_f32(const ivln_gemm_desc* desc, void* stream) {
         if (rc != IVLN_E_UNSUPPORTED || d.tile_override == 6) return rc;
     }
     // short-K 1x1 convs over many pixels: weights in registers, activations streamed (conv1x1_stream.hip)
-    if ((d.tile_override == 0 || d.tile_override == 8) && d.splits <= 1) {  // (tile_override 8 insists on it: tests)
+    // (tile_override 8 insists on it - tests -, forced splits included: the launcher refuses them itself)
+    if ((d.tile_override == 0 && d.splits <= 1) || d.tile_override == 8) {
         const int rc = ivln_conv1x1_stream_launch(d, s, d.tile_override == 8);
         if (rc == IVLN_OK) {
             if (d.splits_used) *d.splits_used = 1;
