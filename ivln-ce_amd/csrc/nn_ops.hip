@@ -9,6 +9,7 @@
 #include <math.h>
 #include "../../include/ivln_hip.h"
 #include "../../include/ivln_rednet_glue.h"
+#include "../../include/ivln_map_sizes.h"
 
 namespace {
 
@@ -1006,6 +1007,86 @@ __global__ __launch_bounds__(256) void k_attn_small(const float* __restrict__ q,
     }
 }
 
+// k_attn_small with a key count per set, each 1 ... 256 (maps other than 64 x 64 cells: (rows/16) * (cols/16) map positions
+// beside the depth grid's 16).  The 256 threads split into IP positions (the power of two >= I, at least 8) x 256 / IP
+// channel parts for the logits, whose parts one thread per position adds in index order; the softmax over up to 256
+// positions goes through one value per wave in LDS, combined in wave order by every thread; then 16 output channels x 16
+// position parts per block as in k_attn_small.  Every order is fixed by the shape alone: two runs give the same bytes.
+struct AttnPairSet {
+    const float* k;
+    const float* v;
+    float* out;
+    int64_t k_img_stride, v_img_stride, ldo;
+    int Ck, Cv, I;
+};
+__global__ __launch_bounds__(256) void k_attn_pair(const float* __restrict__ q, int64_t ldq, float scale,
+                                                   const AttnPairSet s0, const AttnPairSet s1) {
+    __shared__ float qs[1024];
+    __shared__ float part[256];
+    __shared__ float ps[256];
+    __shared__ float wred[8];
+    __shared__ float pl[16][17];
+    const AttnPairSet& S = blockIdx.z == 0 ? s0 : s1;
+    if ((int)blockIdx.y * 16 >= S.Cv) return;  // the two sets may have different output widths
+    const int n = blockIdx.x, I = S.I, tid = threadIdx.x;
+    for (int c = tid; c < S.Ck; c += 256) qs[c] = q[(int64_t)n * ldq + c];
+    __syncthreads();
+    int lg = 3;
+    while ((1 << lg) < I) ++lg;  // I <= 256: lg <= 8
+    const int IP = 1 << lg, NP = 256 >> lg;
+    {
+        const float* kp = S.k + (int64_t)n * S.k_img_stride;
+        const int ti = tid & (IP - 1), tp = tid >> lg;
+        float acc = 0.f;
+        if (ti < I) {
+            int c = tp;
+            for (; c + 7 * NP < S.Ck; c += 8 * NP) {  // (eight loads in flight: at 256 positions a thread walks all of Ck)
+                float kv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) kv[u] = kp[(int64_t)(c + u * NP) * I + ti];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc = fmaf(qs[c + u * NP], kv[u], acc);
+            }
+            for (; c < S.Ck; c += NP) acc = fmaf(qs[c], kp[(int64_t)c * I + ti], acc);
+        }
+        part[tid] = acc;  // (= part[tp][ti])
+    }
+    __syncthreads();
+    float l = -INFINITY;
+    if (tid < I) {
+        float s = 0.f;
+        for (int p = 0; p < NP; ++p) s += part[p * IP + tid];
+        l = s * scale;
+    }
+    const int w = tid >> 6;
+    const float wm = wave_max(l);
+    if ((tid & 63) == 0) wred[w] = wm;
+    __syncthreads();
+    const float mx = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
+    const float e = tid < I ? expf(l - mx) : 0.f;
+    const float wsum = wave_sum(e);
+    if ((tid & 63) == 0) wred[4 + w] = wsum;
+    __syncthreads();
+    const float sum = (wred[4] + wred[5]) + (wred[6] + wred[7]);
+    if (tid < I) ps[tid] = e * (1.f / sum);
+    __syncthreads();
+    const int tc = tid >> 4, tpart = tid & 15;
+    const int c = blockIdx.y * 16 + tc;
+    float acc = 0.f;
+    if (c < S.Cv) {
+        const float* vp = S.v + (int64_t)n * S.v_img_stride + (int64_t)c * I;
+        for (int i = tpart; i < I; i += 16) acc = fmaf(ps[i], vp[i], acc);
+    }
+    pl[tc][tpart] = acc;
+    __syncthreads();
+    if (tpart == 0 && c < S.Cv) {
+        float t = 0.f;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) t += pl[tc][u];
+        S.out[(int64_t)n * S.ldo + c] = t;
+    }
+}
+
 // prev-action embedding: idx = (long)((float(a)+1) * mask) (map_cma_policy.py:297-299)
 __global__ void k_prev_action_embed(const int64_t* __restrict__ prev_actions, const uint8_t* __restrict__ mask,
                                     const float* __restrict__ table, int rows, int E, int n_emb,
@@ -1517,6 +1598,21 @@ int ivln_attn_small2_f32(const float* q, int64_t ldq, float scale, int rows, int
     const int cv = sets == 2 && Cv1 > Cv0 ? Cv1 : Cv0;
     hipLaunchKernelGGL(k_attn_small, dim3(rows, (cv + 15) / 16, sets), dim3(256), 0, (hipStream_t)stream, q, ldq, scale,
                        I, a, b);
+    return LAUNCH_OK();
+}
+
+int ivln_attn_pair_f32(const float* q, int64_t ldq, float scale, int rows, const float* k0, int64_t k0_img_stride,
+                       const float* v0, int64_t v0_img_stride, int Ck0, int Cv0, int I0, float* out0, int64_t ldo0,
+                       const float* k1, int64_t k1_img_stride, const float* v1, int64_t v1_img_stride, int Ck1, int Cv1,
+                       int I1, float* out1, int64_t ldo1, void* stream) {
+    const int sets = k1 ? 2 : 1;
+    if (rows <= 0 || I0 <= 0 || I0 > 256 || Ck0 <= 0 || Ck0 > 1024 || Cv0 <= 0) return IVLN_E_UNSUPPORTED;
+    if (sets == 2 && (I1 <= 0 || I1 > 256 || Ck1 <= 0 || Ck1 > 1024 || Cv1 <= 0)) return IVLN_E_UNSUPPORTED;
+    AttnPairSet a{k0, v0, out0, k0_img_stride, v0_img_stride, ldo0, Ck0, Cv0, I0};
+    AttnPairSet b = sets == 2 ? AttnPairSet{k1, v1, out1, k1_img_stride, v1_img_stride, ldo1, Ck1, Cv1, I1} : a;
+    const int cv = sets == 2 && Cv1 > Cv0 ? Cv1 : Cv0;
+    hipLaunchKernelGGL(k_attn_pair, dim3(rows, (cv + 15) / 16, sets), dim3(256), 0, (hipStream_t)stream, q, ldq, scale, a,
+                       b);
     return LAUNCH_OK();
 }
 

@@ -544,7 +544,7 @@ class GraphedRollout:
         return self.actions
 
     def maps(self):
-        """(occupancy_map, semantic_map) of the last replayed step: the mapper's persistent (B, 64, 64) u8 buffers, as
+        """(occupancy_map, semantic_map) of the last replayed step: the mapper's persistent (B, map rows, map cols) u8 buffers, as
         the captured batch holds them (None, None without a mapper)."""
         batch = self._keep[0] if self.split else getattr(self, "_last_batch", {})
         return batch.get("occupancy_map"), batch.get("semantic_map")

@@ -1459,6 +1459,24 @@ def attn_small2(q, k0, v0, out0, k1, v1, out1, scale):
     )
 
 
+ATTN_PAIR = True  # A/B, tests: False = the head's two attentions of unequal key counts as two ops.attn calls
+ATTN_PAIR_ARGTYPES = [vp, i64, f32, i32, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp]
+
+
+def attn_pair(q, k0, v0, out0, k1=None, v1=None, out1=None, scale=1.0):
+    """attn_small2 with a key count per set, each 1 ... 256 (include/ivln_map_sizes.h): the head's depth and map attentions
+    when the egocentric map is not 64 x 64 cells.  k1 None: set 0 alone."""
+    L = _L()
+    L.ivln_attn_pair_f32.argtypes = ATTN_PAIR_ARGTYPES
+    set1 = ((None, 0, None, 0, 0, 0, 0, None, 0) if k1 is None else
+            (_p(k1), k1.stride(0), _p(v1), v1.stride(0), k1.shape[1], v1.shape[1], v1.shape[2], _p(out1), out1.stride(0)))
+    check(
+        L.ivln_attn_pair_f32(_p(q), q.stride(0), scale, q.shape[0], _p(k0), k0.stride(0), _p(v0), v0.stride(0),
+                             k0.shape[1], v0.shape[1], v0.shape[2], _p(out0), out0.stride(0), *set1, stream_ptr()),
+        "ivln_attn_pair_f32",
+    )
+
+
 def gru_step(x, gi_pre, h_in, mask_u8, w_ih, w_hh, b_ih, b_hh, h_out, h_out2=None, saves=None):
     """One masked GRU step over `rows` rows; x (rows,I) or gi_pre (rows,3H); h_in/h_out strided."""
     rows = h_in.shape[0]

@@ -107,6 +107,7 @@ class MapCMANet(Net):
             observation_space, sm.num_semantic_classes, sm.channels, sm.last_ch_mult, sm.trainable, sm.from_pretrained,
             sm.checkpoint,
         )
+        self.check_map_size(observation_space.spaces["occupancy_map"].shape)
         self.instruction_encoder = InstructionEncoder(model_config.INSTRUCTION_ENCODER)
         assert model_config.DEPTH_ENCODER.cnn_type in [
             "VlnResnetDepthEncoder"
@@ -172,6 +173,19 @@ class MapCMANet(Net):
         if not model_config.SEMANTIC_MAP_ENCODER.trainable:
             self.map_encoder.eval()
         self._scale_f = float(1.0 / ((hidden_size // 2) ** 0.5))
+
+    @staticmethod
+    def check_map_size(map_shape):
+        """Raises for egocentric maps the map branch cannot take: the map CNN halves the plane four times and its pooling
+        tail reads pixel pairs (an odd plane is refused by the kernel, where the reference's AvgPool2d floors), and the
+        head's map attention covers up to 256 positions."""
+        rows, cols = int(map_shape[0]), int(map_shape[1])
+        n_pos = (rows // 16) * (cols // 16)
+        if rows <= 0 or cols <= 0 or rows % 16 or cols % 16 or n_pos > 256:
+            raise ValueError(
+                f"EGOCENTRIC_MAPPER.height_meters / width_meters / resolution_meters give a map of {rows} x {cols} cells "
+                f"(height_meters / resolution_meters x width_meters / resolution_meters); MapCMANet takes maps whose sides "
+                f"are multiples of 16 cells with (rows // 16) * (cols // 16) <= 256 attention positions (here {n_pos})")
 
     @property
     def output_size(self):
@@ -239,7 +253,8 @@ class MapCMANet(Net):
             return
         rows, L = example_obs[key].shape[0], example_obs[key].shape[1]
         P = self.depth_encoder.output_shape[1] * self.depth_encoder.output_shape[2]
-        if P > 16 or L > 512:
+        Pm = self.map_encoder.output_shape[1] * self.map_encoder.output_shape[2]
+        if P > 16 or Pm != P or L > 512:
             return  # outside the fused head's envelope: the step takes the unfused chain
         self._cma_fold_weights()
         head[0](rows, L, P, self._hidden_size, example_obs[key].device)
@@ -376,10 +391,11 @@ class MapCMANet(Net):
         (txt, lengths, tk), (dep, dkv), (mp, mkv) = txt3, dep2, map2
         geo, dev = self.step_geometry, rnn_states.device
         H, h2, rows = self._hidden_size, self._hidden_size // 2, masks_u8.shape[0]
-        L, P = txt.shape[2], dep.shape[2] * dep.shape[3]
+        # (two key counts: the depth grid's P, and the map's Pm = (rows / 16) * (cols / 16) cells of the egocentric map)
+        L, P, Pm = txt.shape[2], dep.shape[2] * dep.shape[3], mp.shape[2] * mp.shape[3]
         rnn_out = torch.empty_like(rnn_states) if rnn_out is None else rnn_out
         feats = torch.empty((rows, H), dtype=torch.float32, device=dev)
-        if fused_head and P <= 16 and L <= 512 and tk.shape[1] == H + 1 + h2:
+        if fused_head and P <= 16 and Pm == P and L <= 512 and tk.shape[1] == H + 1 + h2:
             # GRU-1 -> text attention -> depth / map attention -> compress -> GRU-2 as one C-ABI call (five phase kernels,
             # csrc/cma_step.hip); `tk` holds the folded [Mq | TQb] operand here.  With LSTM encoders the same descriptor
             # goes to the LSTM form: 4H weight rows, and the (rows, 4, H) states [h1 | c1 | h2 | c2]
@@ -413,14 +429,17 @@ class MapCMANet(Net):
         text = x2[:, geo.o_txt:geo.o_dep]
         ops.attn(q1, tk.view(tk.shape[0], h2, L), txt, lengths, self._scale_f, text, a_txt, row_index=inv)
 
-        dkv, mkv = dkv.view(rows, -1, P), mkv.view(rows, -1, P)
+        dkv, mkv = dkv.view(rows, -1, P), mkv.view(rows, -1, Pm)
         q2 = ops.linear(text, self.text_q.weight, self.text_q.bias)
         a_dep = torch.empty((rows, P), dtype=torch.float32, device=dev) if save is not None else None
-        a_map = torch.empty((rows, P), dtype=torch.float32, device=dev) if save is not None else None
+        a_map = torch.empty((rows, Pm), dtype=torch.float32, device=dev) if save is not None else None
         x2_dep, x2_map = x2[:, geo.o_dep:geo.o_map], x2[:, geo.o_map:geo.o_prev]
-        if save is None and P <= 32:
+        if save is None and Pm == P and P <= 32:
             # rollout head: both short-axis attentions (they share the query) in one launch
             ops.attn_small2(q2, dkv[:, :h2], dkv[:, h2:], x2_dep, mkv[:, :h2], mkv[:, h2:], x2_map, self._scale_f)
+        elif save is None and ops.ATTN_PAIR and max(P, Pm) <= 256:
+            # a map of another size: the same launch with a key count per set (include/ivln_map_sizes.h)
+            ops.attn_pair(q2, dkv[:, :h2], dkv[:, h2:], x2_dep, mkv[:, :h2], mkv[:, h2:], x2_map, self._scale_f)
         else:
             ops.attn(q2, dkv[:, :h2], dkv[:, h2:], None, self._scale_f, x2_dep, a_dep)
             ops.attn(q2, mkv[:, :h2], mkv[:, h2:], None, self._scale_f, x2_map, a_map)
@@ -434,7 +453,7 @@ class MapCMANet(Net):
             save.update(
                 g1=s_g1, g2=s_g2, dep=dep, mp=mp, txt_out=txt, lengths=lengths,
                 state_in=state_in, x2=x2, q1=q1, tk=tk, a_txt=a_txt, dkv=dkv, mkv=mkv, q2=q2, a_dep=a_dep,
-                a_map=a_map, c2=c2, feats=feats, rows=rows, L=L, P=P,
+                a_map=a_map, c2=c2, feats=feats, rows=rows, L=L, P=P, Pm=Pm,
                 offs=(geo.o_txt, geo.o_dep, geo.o_map, geo.o_prev), masks=masks_u8, inv=inv,
             )
         return feats, rnn_out

@@ -376,7 +376,7 @@ def net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
 
 def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     G: Dict = {}
-    rows, L, P = S["rows"], S["L"], S["P"]
+    rows, L, P, Pm = S["rows"], S["L"], S["P"], S["Pm"]  # (key positions: depth grid, egocentric map)
     H = net._hidden_size
     h2 = H // 2
     scale = net._scale_f
@@ -463,8 +463,8 @@ def _net_backward(net, S: Dict, d_feats: torch.Tensor) -> Dict:
     G[ml.weight] = ops.linear_bwd_weight(d_pre_m, mp.view(rows, -1))
     G[ml.bias] = _colsum(d_pre_m)
     d_mp = ops.linear_bwd_input(d_pre_m, ml.weight)
-    d_mp = _conv1d_backward(net.map_kv, d_mkv.view(rows, -1, 1, P), mp.view(rows, Cm, 1, P),
-                            d_mp.view(rows, Cm, 1, P), G)
+    d_mp = _conv1d_backward(net.map_kv, d_mkv.view(rows, -1, 1, Pm), mp.view(rows, Cm, 1, Pm),
+                            d_mp.view(rows, Cm, 1, Pm), G)
     if any(p.requires_grad for p in net.map_encoder.parameters()):
         d = d_mp.view(mp.shape)
         blocks = list(net.map_encoder.cnn)
