@@ -48,6 +48,10 @@ def _sig(L):
     L.ivln_mapper_known_attach.argtypes = [vp, vp]
     L.ivln_mapper_known_step.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.ivln_mapper_known_count.argtypes = [vp, i32, C.POINTER(i64), vp]
+    # include/ivln_map_build.h
+    L.ivln_mapper_env_counts.argtypes = [vp, i32, C.POINTER(i64), vp]
+    L.ivln_mapper_env_export.argtypes = [vp, i32, vp, vp, i64, C.POINTER(i64), vp]
+    L.ivln_known_lib_add_from_mapper.argtypes = [vp, i32, vp, i32, vp, i64, vp]
 
 
 def lib():

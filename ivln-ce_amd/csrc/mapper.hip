@@ -26,6 +26,7 @@
 #include <new>
 #include "../../include/ivln_hip.h"
 #include "../../include/ivln_known_lib.h"
+#include "../../include/ivln_map_build.h"
 
 namespace {
 
@@ -697,6 +698,143 @@ __global__ void k_known_count(const int* __restrict__ cur, const KScene* __restr
     *out = s;
 }
 
+// ---- known-map builder (include/ivln_map_build.h): env b's points in ascending rank, compacted on the device.
+// Between complete steps rank == key of the last keep-highest: unique, < table_cells, and tab64 is all zero.  So env b's
+// points mark slot (key - lowest key of b) of tab64 with (index in the cloud + 1), an exclusive scan of "slot is marked"
+// over the window [lowest, highest] is each point's place in the output, and the scatter clears the marks it consumes.
+// The scan is hierarchical over tiles of kThreads entries with one LAUNCH per level and direction (count up, scan the top
+// tile, scan down, scatter): a workgroup only ever reads what an earlier launch wrote and never waits on another one.
+// Everything is bounds-checked against the cloud size, the window and max_n, whatever the table holds. ----
+constexpr int kStatBlocks = 128;  // workgroups (and host-summed partials per env) of k_env_stats
+
+// per block and env: {count, lowest rank, highest rank} -> part[(block * B_max + b) * 3]; the host folds the blocks
+__global__ __launch_bounds__(kThreads) void k_env_stats(const Pt* __restrict__ w0, const Pt* __restrict__ w1,
+                                                        const int64_t* __restrict__ r0, const int64_t* __restrict__ r1,
+                                                        const Scalars* __restrict__ sc, unsigned capacity, int B_max,
+                                                        unsigned* __restrict__ part) {
+    __shared__ unsigned st[kBoxEnvs][3];
+    for (int i = threadIdx.x; i < B_max; i += kThreads) {
+        st[i][0] = 0u; st[i][1] = 0xFFFFFFFFu; st[i][2] = 0u;
+    }
+    __syncthreads();
+    const int cur = sc->cur & 1;
+    const Pt* wsrc = cur ? w1 : w0;
+    const int64_t* rsrc = cur ? r1 : r0;
+    const unsigned n = min(sc->cnt[cur], capacity);
+    for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const unsigned b = wsrc[i].meta >> 8;
+        if (b >= (unsigned)B_max) continue;
+        const int64_t r = rsrc[i];
+        const unsigned k = (r < 0 || r > 0xFFFFFFFFll) ? 0xFFFFFFFFu : (unsigned)r;  // (not a key: the host refuses it)
+        atomicAdd(&st[b][0], 1u);  // LDS integer atomics: the result does not depend on their order
+        if (k < st[b][1]) atomicMin(&st[b][1], k);
+        if (k > st[b][2]) atomicMax(&st[b][2], k);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < B_max * 3; i += kThreads) part[(size_t)blockIdx.x * B_max * 3 + i] = st[i / 3][i % 3];
+}
+
+__global__ __launch_bounds__(kThreads) void k_env_mark(const Pt* __restrict__ w0, const Pt* __restrict__ w1,
+                                                       const int64_t* __restrict__ r0, const int64_t* __restrict__ r1,
+                                                       const Scalars* __restrict__ sc, unsigned capacity, unsigned b,
+                                                       unsigned kmin, unsigned window,
+                                                       unsigned long long* __restrict__ tab64) {
+    const int cur = sc->cur & 1;
+    const Pt* wsrc = cur ? w1 : w0;
+    const int64_t* rsrc = cur ? r1 : r0;
+    const unsigned n = min(sc->cnt[cur], capacity);
+    for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        if ((wsrc[i].meta >> 8) != b) continue;
+        const int64_t off = rsrc[i] - (int64_t)kmin;
+        if (off < 0 || off >= (int64_t)window) continue;
+        tab64[off] = (unsigned long long)i + 1ull;  // unique keys: one writer per slot
+    }
+}
+
+// Exclusive scan of v over the block's threads (wave shuffles + 4 wave sums in LDS); *total = the block's sum.
+__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* total) {
+    __shared__ unsigned wsum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    unsigned base = 0;
+    for (int i = 0; i < w; ++i) base += wsum[i];
+    if (total) *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();  // wsum is reused by the next call
+    return base + inc - v;
+}
+
+// up: dst[j] = sum of tile j (kThreads entries) of the level below - marks of the table (MARKS) or partial sums
+template <bool MARKS>
+__global__ __launch_bounds__(kThreads) void k_scan_up(const unsigned long long* __restrict__ marks,
+                                                      const unsigned* __restrict__ src, unsigned n,
+                                                      unsigned* __restrict__ dst) {
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;
+    unsigned v = 0;
+    if (i < n) v = MARKS ? (marks[i] != 0ull ? 1u : 0u) : src[i];
+    unsigned total;
+    (void)block_excl_scan(v, &total);
+    if (threadIdx.x == 0) dst[blockIdx.x] = total;
+}
+
+// top: one workgroup, n <= kThreads entries, exclusive scan in place
+__global__ __launch_bounds__(kThreads) void k_scan_top(unsigned* __restrict__ p, unsigned n) {
+    const unsigned v = threadIdx.x < n ? p[threadIdx.x] : 0u;
+    const unsigned e = block_excl_scan(v, nullptr);
+    if (threadIdx.x < n) p[threadIdx.x] = e;
+}
+
+// down: tile j of p becomes its exclusive scan + parent[j] (parent: the scanned level above), in place
+__global__ __launch_bounds__(kThreads) void k_scan_down(unsigned* __restrict__ p, unsigned n,
+                                                        const unsigned* __restrict__ parent) {
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;
+    const unsigned v = i < n ? p[i] : 0u;
+    const unsigned e = block_excl_scan(v, nullptr) + parent[blockIdx.x];
+    if (i < n) p[i] = e;
+}
+
+// scatter: marked slot i of the window -> output row base[tile] + (marked slots in front of it in the tile); the mark is
+// cleared.  REC: 16-byte library records (x, y, z, label), else xyz f32 (n, 3) + sem u8 (n).
+template <bool REC>
+__global__ __launch_bounds__(kThreads) void k_env_scatter(unsigned long long* __restrict__ tab64, unsigned window,
+                                                          const unsigned* __restrict__ base, const Pt* __restrict__ w0,
+                                                          const Pt* __restrict__ w1, const Scalars* __restrict__ sc,
+                                                          unsigned capacity, float* __restrict__ xyz,
+                                                          uint8_t* __restrict__ sem, Pt* __restrict__ rec, int64_t max_n) {
+    const int cur = sc->cur & 1;
+    const Pt* wsrc = cur ? w1 : w0;
+    const unsigned n = min(sc->cnt[cur], capacity);
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;
+    unsigned long long v = 0ull;
+    if (i < window) {
+        v = tab64[i];
+        if (v != 0ull) tab64[i] = 0ull;  // the table is the step kernels' again: all zero
+    }
+    const unsigned dst = block_excl_scan(v != 0ull ? 1u : 0u, nullptr) + base[blockIdx.x];
+    if (v == 0ull || v - 1ull >= (unsigned long long)n || (int64_t)dst >= max_n) return;
+    const Pt p = wsrc[v - 1ull];
+    if (REC) {
+        Pt q = p;
+        q.meta = p.meta & 0xFFu;
+        rec[dst] = q;
+    } else {
+        xyz[3 * (size_t)dst] = p.x; xyz[3 * (size_t)dst + 1] = p.y; xyz[3 * (size_t)dst + 2] = p.z;
+        sem[dst] = (uint8_t)(p.meta & 0xFFu);
+    }
+}
+
+__global__ void k_known_entry(KScene* entry, const Pt* rec, int n) {  // (read by launches BEHIND this one on the stream)
+    entry->rec = rec;
+    entry->n = n;
+    entry->present = 1;
+}
+
 }  // namespace
 
 struct ivln_known_lib {
@@ -726,6 +864,10 @@ struct ivln_mapper {
     int* kcur;          // latched scene index per row (-1: none)
     float* krot;        // ego rotation per row, derived by the step's first launch
     long long* kcount;  // result word of ivln_mapper_known_count
+    // known-map builder (include/ivln_map_build.h); allocated by its first call
+    unsigned* env_part;       // device: per-block, per-env {count, lowest rank, highest rank} of k_env_stats
+    unsigned* env_part_host;  // host copy the blocks are folded from
+    unsigned* scan_buf;       // device: the scan's levels above the marks, level 1 first
 };
 
 #define HIPCHK(x)                          \
@@ -783,6 +925,7 @@ int ivln_mapper_create(int B_max, int H, int W, double vfov_rad, double height_m
     if (m->table_cells > (1ll << 31)) m->table_cells = 1ll << 31;  // ranks = keys must fit 31 bits (k_world_max)
     m->known_rank = 0;
     m->klib = nullptr; m->kcur = nullptr; m->krot = nullptr; m->kcount = nullptr;
+    m->env_part = nullptr; m->env_part_host = nullptr; m->scan_buf = nullptr;
     m->local_blocks = m->world_blocks = 0;
     // core.py:70-115: intrinsics in python doubles -> fp32; (u + 0.5 - cx) / fx in fp32
     double hfov = (double)W / (double)H * vfov_rad;
@@ -840,6 +983,9 @@ int ivln_mapper_destroy(ivln_mapper* m) {
     if (m->kcur) (void)hipFree(m->kcur);
     if (m->krot) (void)hipFree(m->krot);
     if (m->kcount) (void)hipFree(m->kcount);
+    if (m->env_part) (void)hipFree(m->env_part);
+    if (m->scan_buf) (void)hipFree(m->scan_buf);
+    free(m->env_part_host);
     delete m;
     return IVLN_OK;
 }
@@ -1111,6 +1257,142 @@ int ivln_mapper_world_export(ivln_mapper* m, float* xyz, uint32_t* meta, int64_t
         HIPCHK(hipMemcpyAsync(rank, m->rbuf[cur], sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
+    return IVLN_OK;
+}
+
+// ---- known-map builder (include/ivln_map_build.h) ----
+struct EnvStat {
+    int64_t n;
+    uint32_t kmin, kmax;
+};
+
+static int builder_scratch(ivln_mapper* m) {
+    if (m->env_part) return IVLN_OK;
+    const size_t part = (size_t)kStatBlocks * m->B_max * 3;
+    size_t levels = 0;  // entries of every scan level above a window of table_cells marks
+    for (int64_t n = m->table_cells;;) {
+        n = (n + kThreads - 1) / kThreads;
+        levels += (size_t)n;
+        if (n <= kThreads) break;
+    }
+    unsigned *dp = nullptr, *ds = nullptr;
+    unsigned* hp = (unsigned*)malloc(sizeof(unsigned) * part);
+    if (!hp || hipMalloc(&dp, sizeof(unsigned) * part) != hipSuccess || hipMalloc(&ds, sizeof(unsigned) * levels) != hipSuccess) {
+        free(hp);
+        (void)hipFree(dp);
+        (void)hipFree(ds);
+        return IVLN_E_HIP;
+    }
+    m->env_part = dp; m->env_part_host = hp; m->scan_buf = ds;
+    return IVLN_OK;
+}
+
+// One launch + one read-back (synchronises): st[b] for every b < B_max, *total = points of the cloud.
+static int env_stats(ivln_mapper* m, EnvStat* st, int64_t* total, hipStream_t s) {
+    const int rc = builder_scratch(m);
+    if (rc != IVLN_OK) return rc;
+    hipLaunchKernelGGL(k_env_stats, dim3(kStatBlocks), dim3(kThreads), 0, s, m->wbuf[0], m->wbuf[1], m->rbuf[0], m->rbuf[1],
+                       m->sc, (unsigned)m->capacity, m->B_max, m->env_part);
+    if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
+    const size_t part = (size_t)kStatBlocks * m->B_max * 3;
+    HIPCHK(hipMemcpyAsync(m->env_part_host, m->env_part, sizeof(unsigned) * part, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *total = 0;
+    for (int b = 0; b < m->B_max; ++b) {
+        EnvStat e{0, 0xFFFFFFFFu, 0u};
+        for (int k = 0; k < kStatBlocks; ++k) {
+            const unsigned* p = m->env_part_host + ((size_t)k * m->B_max + b) * 3;
+            e.n += p[0];
+            if (p[1] < e.kmin) e.kmin = p[1];
+            if (p[2] > e.kmax) e.kmax = p[2];
+        }
+        st[b] = e;
+        *total += e.n;
+    }
+    return IVLN_OK;
+}
+
+// mark / scan / scatter of env b (e.n <= max_n was checked); xyz + sem, or rec
+static int env_compact(ivln_mapper* m, int b, const EnvStat& e, int64_t total, float* xyz, uint8_t* sem, Pt* rec,
+                       int64_t max_n, hipStream_t s) {
+    if (e.n == 0) return IVLN_OK;
+    if (e.kmin > e.kmax || (int64_t)e.kmax >= m->table_cells) return IVLN_E_UNSUPPORTED;  // ranks that are not keys
+    const unsigned window = e.kmax - e.kmin + 1u;  // <= table_cells <= 2^31
+    const unsigned cap = (unsigned)m->capacity;
+    int mb = (int)((total + kThreads - 1) / kThreads);
+    if (mb > kWorldBlocks) mb = kWorldBlocks;
+    hipLaunchKernelGGL(k_env_mark, dim3(mb), dim3(kThreads), 0, s, m->wbuf[0], m->wbuf[1], m->rbuf[0], m->rbuf[1], m->sc, cap,
+                       (unsigned)b, e.kmin, window, m->tab64);
+    // levels of the scan: cnt[0] marks, cnt[k + 1] = tiles of level k, until one tile holds the top level
+    unsigned cnt[8];
+    unsigned* lvl[8];
+    int top = 0;
+    cnt[0] = window;
+    lvl[0] = nullptr;
+    unsigned* next = m->scan_buf;
+    do {
+        cnt[top + 1] = (cnt[top] + kThreads - 1) / kThreads;
+        lvl[top + 1] = next;
+        next += cnt[top + 1];
+        ++top;
+    } while (cnt[top] > (unsigned)kThreads);
+    hipLaunchKernelGGL(k_scan_up<true>, dim3(cnt[1]), dim3(kThreads), 0, s, m->tab64, (const unsigned*)nullptr, window, lvl[1]);
+    for (int k = 1; k < top; ++k)
+        hipLaunchKernelGGL(k_scan_up<false>, dim3(cnt[k + 1]), dim3(kThreads), 0, s, (const unsigned long long*)nullptr, lvl[k],
+                           cnt[k], lvl[k + 1]);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kThreads), 0, s, lvl[top], cnt[top]);
+    for (int k = top - 1; k >= 1; --k)
+        hipLaunchKernelGGL(k_scan_down, dim3(cnt[k + 1]), dim3(kThreads), 0, s, lvl[k], cnt[k], lvl[k + 1]);
+    if (rec)
+        hipLaunchKernelGGL(k_env_scatter<true>, dim3(cnt[1]), dim3(kThreads), 0, s, m->tab64, window, lvl[1], m->wbuf[0],
+                           m->wbuf[1], m->sc, cap, (float*)nullptr, (uint8_t*)nullptr, rec, max_n);
+    else
+        hipLaunchKernelGGL(k_env_scatter<false>, dim3(cnt[1]), dim3(kThreads), 0, s, m->tab64, window, lvl[1], m->wbuf[0],
+                           m->wbuf[1], m->sc, cap, xyz, sem, (Pt*)nullptr, max_n);
+    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+}
+
+int ivln_mapper_env_counts(ivln_mapper* m, int B, int64_t* counts_host, void* stream) {
+    if (!m || !counts_host || B <= 0 || B > m->B_max) return IVLN_E_INVALID;
+    EnvStat st[kBoxEnvs];
+    int64_t total = 0;
+    const int rc = env_stats(m, st, &total, (hipStream_t)stream);
+    if (rc != IVLN_OK) return rc;
+    for (int b = 0; b < B; ++b) counts_host[b] = st[b].n;
+    return IVLN_OK;
+}
+
+int ivln_mapper_env_export(ivln_mapper* m, int b, float* xyz, uint8_t* sem, int64_t max_n, int64_t* n_out, void* stream) {
+    if (!m || !n_out || b < 0 || b >= m->B_max || max_n < 0 || (max_n > 0 && (!xyz || !sem))) return IVLN_E_INVALID;
+    if (m->known_rank != 0) return IVLN_E_UNSUPPORTED;
+    EnvStat st[kBoxEnvs];
+    int64_t total = 0;
+    const int rc = env_stats(m, st, &total, (hipStream_t)stream);
+    if (rc != IVLN_OK) return rc;
+    *n_out = st[b].n;
+    if (st[b].n > max_n) return IVLN_E_CAPACITY;
+    return env_compact(m, b, st[b], total, xyz, sem, nullptr, max_n, (hipStream_t)stream);
+}
+
+int ivln_known_lib_add_from_mapper(ivln_known_lib* lib, int scene, ivln_mapper* m, int b, void* records, int64_t max_n,
+                                   void* stream) {
+    if (!lib || !m || scene < 0 || scene >= lib->max_scenes || lib->added[scene] || b < 0 || b >= m->B_max || max_n < 0)
+        return IVLN_E_INVALID;
+    if (max_n > 0 && (!records || ((uintptr_t)records & 15u))) return IVLN_E_INVALID;
+    if (m->known_rank != 0) return IVLN_E_UNSUPPORTED;
+    EnvStat st[kBoxEnvs];
+    int64_t total = 0;
+    int rc = env_stats(m, st, &total, (hipStream_t)stream);
+    if (rc != IVLN_OK) return rc;
+    if (st[b].n > max_n) return IVLN_E_CAPACITY;
+    if (st[b].n >= (1ll << 31)) return IVLN_E_INVALID;  // (a library scene holds < 2^31 points: ivln_known_lib_add)
+    rc = env_compact(m, b, st[b], total, nullptr, nullptr, (Pt*)records, max_n, (hipStream_t)stream);
+    if (rc != IVLN_OK) return rc;
+    hipLaunchKernelGGL(k_known_entry, dim3(1), dim3(1), 0, (hipStream_t)stream, lib->table + scene, (const Pt*)records,
+                       (int)st[b].n);
+    if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
+    lib->added[scene] = 1;
+    lib->n_added += 1;
     return IVLN_OK;
 }
 

@@ -86,6 +86,20 @@ def load_known_scene(maps_location, env_name):
     return xyz, sem
 
 
+def save_known_scene(maps_location, env_name, xyz, semantics):
+    """The inverse of `load_known_scene`: writes {maps_location}/{env_name}.npz with the keys known-map mode reads,
+    `xyz` (n, 3) float32 and `semantics` (n,) int64 - the reference builds `torch.LongTensor(f["semantics"])`
+    (mapper.py:283-294), which takes an int64 array and nothing narrower.  Row order is file order.  Returns the path."""
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+    sem = np.ascontiguousarray(np.asarray(semantics).reshape(-1).astype(np.int64))
+    if xyz.shape[0] != sem.shape[0]:
+        raise ValueError(f"scene {env_name}: {xyz.shape[0]} points but {sem.shape[0]} labels")
+    os.makedirs(maps_location, exist_ok=True)
+    path = os.path.join(maps_location, f"{env_name}.npz")
+    np.savez(path, xyz=xyz, semantics=sem)
+    return path
+
+
 class KnownSceneLibrary:
     """Device-resident scene clouds of known-map mode, each held once (include/ivln_known_lib.h).  The host side is a
     dict name -> index; a scene is read from `{maps_location}/{name}.npz` the first time its name is seen, packed on the
@@ -154,6 +168,28 @@ class KnownSceneLibrary:
             self._index[name] = i
         return i
 
+    def _add_from_mapper(self, scene, mapping_module, b, records):
+        """The C call (tests replace it with a stub): ordered compaction of row b's cloud into `records` + table entry."""
+        check(lib().ivln_known_lib_add_from_mapper(self.handle(), scene, mapping_module._h, int(b), records.data_ptr(),
+                                                   records.shape[0], stream_ptr()), "ivln_known_lib_add_from_mapper")
+
+    def add_from_mapper(self, name, mapping_module, b) -> int:
+        """Promotes the cloud that row `b` of an iterative `MappingModule` has explored to scene `name`, in the reference's cloud
+        order and without a host copy of the points (include/ivln_map_build.h): asks for the count, allocates the records,
+        one C call on the current stream.  A captured step replayed behind this call sees the scene.  Returns its index; a
+        name that is already present raises (an entry a captured step may be reading is never rewritten)."""
+        if name in self._index:
+            raise _lib.IvlnError(f"known-scene library already holds scene {name!r}")
+        i = len(self._index)
+        if i >= self.max_scenes:
+            raise _lib.IvlnError(f"known-scene library is full ({self.max_scenes} scenes)")
+        n = int(mapping_module.env_counts()[b])
+        records = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        self._add_from_mapper(i, mapping_module, b, records)
+        self._records.append(records)
+        self._index[name] = i
+        return i
+
 
 class MappingModule:
     """Drop-in for mapper.py:904-944 (`create_*_mapper` factories :950-1028).
@@ -180,6 +216,7 @@ class MappingModule:
         world_capacity: int = 0,
         table_cells: int = 0,
         known_library: bool = False,
+        scene_library: Optional[KnownSceneLibrary] = None,
     ):
         if device.type != "cuda":
             raise _lib.IvlnError("the HIP mapper needs a GPU device (no CPU fallback)")
@@ -200,9 +237,11 @@ class MappingModule:
         self._T = torch.empty((b_max, 4, 4), dtype=torch.float32, device=device)
         self._rot = torch.empty((b_max, 3, 3), dtype=torch.float32, device=device)
         self._known_cache: Dict[str, tuple] = {}
+        self._begin_open = False  # a `begin` whose `finish` has not run: the cloud cannot be exported (export_scene)
         self.known_library = bool(known_library) and mode == "known"
         if self.known_library:
-            self.scene_library = KnownSceneLibrary(device, maps_location)
+            # (scene_library: one that exists already, e.g. filled by `add_from_mapper`; names it lacks are read from files)
+            self.scene_library = scene_library if scene_library is not None else KnownSceneLibrary(device, maps_location)
             self._scene_dev = torch.full((b_max,), -1, dtype=torch.int32, device=device)  # the step's scene index per row
             # pinned staging rows, used in turn: a row is rewritten only after the copy that read it has run
             self._scene_pin = [torch.zeros((b_max,), dtype=torch.int32).pin_memory() for _ in range(4)]
@@ -384,6 +423,7 @@ class MappingModule:
         orientation = observations["world_robot_orientation"].to(self.device, torch.float64).contiguous()
         # (finish reads pose / T / rot through the pointers begin was given: they stay alive on the module)
         self._open = (depth, not_done, pose, orientation)
+        self._begin_open = True
         check(lib().ivln_mapper_step_begin(self._h, dptr(depth), dptr(pose), dptr(orientation), dptr(not_done), B,
                                            dptr(self.map_memory._occ), dptr(self._T), dptr(self._rot), stream_ptr()),
               "ivln_mapper_step_begin")
@@ -409,6 +449,7 @@ class MappingModule:
         check(lib().ivln_mapper_step_finish(self._h, dptr(depth_c), dptr(labels), dptr(self._T), dptr(pose), dptr(self._rot),
                                             dptr(not_done), B, dptr(mem._occ), dptr(mem._sem), stream_ptr()),
               "ivln_mapper_step_finish")
+        self._begin_open = False
         return mem
 
     def _load_known(self, env_name):
@@ -453,6 +494,36 @@ class MappingModule:
         xyz, meta, rank = xyz[:n].cpu().numpy(), meta[:n].cpu().numpy().view(np.uint32), rank[:n].cpu().numpy()
         order = np.argsort(rank, kind="stable")
         return xyz[order], (meta[order] >> 8).astype(np.int32), (meta[order] & 0xFF).astype(np.uint8)
+
+    # -- known-map builder (include/ivln_map_build.h): the explored cloud per row, in the reference's order ---------------
+    def _exportable(self, what):
+        if self.mode != "iterative":
+            raise _lib.IvlnError(f"MappingModule.{what}: iterative mode only (a known-mode cloud is not ordered by key)")
+        if self._begin_open:
+            raise _lib.IvlnError(f"MappingModule.{what}: `begin` is open - the cloud is defined between complete steps only")
+        if self._h is None:
+            raise _lib.IvlnError(f"MappingModule.{what}: no step has run yet")
+
+    def env_counts(self) -> np.ndarray:
+        """Points of every row's cloud: (b_max,) int64.  One launch + one read-back; synchronises."""
+        self._exportable("env_counts")
+        counts = (C.c_int64 * self.b_max)()
+        check(lib().ivln_mapper_env_counts(self._h, self.b_max, counts, stream_ptr()), "ivln_mapper_env_counts")
+        return np.array(counts[:], dtype=np.int64)
+
+    def export_scene(self, b: int):
+        """Row b's cloud in the reference's order, ordered and compacted on the device: xyz (n, 3) float32, semantics (n,)
+        uint8 - the arrays of a known-map file (`save_known_scene`)."""
+        self._exportable("export_scene")
+        if not 0 <= int(b) < self.b_max:
+            raise _lib.IvlnError(f"row {b} outside [0, {self.b_max})")
+        n = int(self.env_counts()[b])
+        xyz = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
+        sem = torch.empty((max(n, 1),), dtype=torch.uint8, device=self.device)
+        nn = C.c_int64(0)
+        check(lib().ivln_mapper_env_export(self._h, int(b), dptr(xyz), dptr(sem), n, C.byref(nn), stream_ptr()),
+              "ivln_mapper_env_export")
+        return xyz[:n].cpu().numpy(), sem[:n].cpu().numpy()
 
 
 def create_gt_semantics_iterative_mapper(device, camera_parameters, map_dimensions, **kw) -> MappingModule:
