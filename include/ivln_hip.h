@@ -727,7 +727,12 @@ int ivln_rednet_fwd(const ivln_rednet_op* table, int n_ops, const uint8_t* rgb, 
  * dkv (rows, Hq+d_out, P) / mkv (rows, Hq+m_out, P) = the dep_kv / map_kv projections (keys first).
  * Outputs: x2 (rows, x2w) = [state | text | dep' | map' | prev] (the prev slice is the caller's), h_out (rows, 2, H)
  * row stride ld_ho, feats (rows, H).  ws: ivln_cma_step_ws_floats() floats of scratch (128-byte aligned).
- * IVLN_E_UNSUPPORTED outside L <= 512, P <= 16, 64-aligned widths; IVLN_E_INVALID for a NULL h_in / h_out / x2 / feats / ws. */
+ * Envelope: IVLN_E_UNSUPPORTED outside 1 <= L <= 512, 1 <= P <= 16, H > 0 and a multiple of 64, Hq / Ct / d_out / m_out
+ * multiples of 16, d_out + m_out + E, x2w and ld_h multiples of 4, x2w = H + Ct + d_out + m_out + E; IVLN_E_INVALID for
+ * rows <= 0, a NULL h_in / h_out / x2 / feats / ws, a row stride ld_h / ld_ho below 2H, or h_in / h_out row ranges that
+ * overlap (every workgroup reads whole rows of h_in while others write h_out).  Mq_img / TQb_img <= 0 stand for the
+ * contiguous strides (H + 1) * L and Hq * L.  Nothing is launched when a code other than IVLN_OK / IVLN_E_HIP is
+ * returned. */
 typedef struct ivln_cma_step_desc {
     int rows, L, P, H, Hq, Ct, d_out, m_out, E, x2w;
     const float* state_in;
@@ -763,10 +768,9 @@ int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream);
  * else (folds, operands, x2, feats) as above.  ws: ivln_cma_step_lstm_ws_floats() floats.  Its layout is a superset of
  * the GRU form's: [logits | S | rows x 3H, unused here | c2], which the shared phase kernels address as they always did,
  * followed by the hidden half of LSTM-2 (rows x 4H); ivln_cma_step_lstm_ws_floats = ivln_cma_step_ws_floats + that
- * region, rounded up to 128-byte lines.  Same envelope as ivln_cma_step_fwd, and in addition IVLN_E_UNSUPPORTED for ld_ho % 4 != 0 and
- * IVLN_E_INVALID for a NULL h_in / h_out, a row stride below 4H, or h_in / h_out row ranges that overlap (every
- * workgroup reads whole rows of h_in while others write h_out).  Nothing is launched when a code other than IVLN_OK /
- * IVLN_E_HIP is returned. */
+ * region, rounded up to 128-byte lines.  Same envelope as ivln_cma_step_fwd with the state 4H wide (IVLN_E_INVALID for
+ * a row stride below 4H, or (rows, 4, H) row ranges of h_in / h_out that overlap), and in addition IVLN_E_UNSUPPORTED
+ * for ld_ho % 4 != 0. */
 int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H);
 int ivln_cma_step_lstm_fwd(const ivln_cma_step_desc* d, int mode, void* stream);
 

@@ -415,6 +415,17 @@ int check_desc(const Desc* d) {
     return IVLN_OK;
 }
 
+// ... and of its state views, G floats per row (2H: GRU, 4H: LSTM).  Every workgroup reads whole rows of h_in while
+// others write h_out: the two views must not share memory.
+int check_state(const Desc* d, int64_t G) {
+    if (d->H <= 0) return IVLN_E_UNSUPPORTED;   // (H = 0 passes H & 63 and would reach a launch with an empty grid)
+    if (d->ld_h < G || d->ld_ho < G) return IVLN_E_INVALID;
+    const float *in0 = d->h_in, *in1 = d->h_in + (int64_t)(d->rows - 1) * d->ld_h + G;
+    const float *out0 = d->h_out, *out1 = d->h_out + (int64_t)(d->rows - 1) * d->ld_ho + G;
+    if ((uintptr_t)in0 < (uintptr_t)out1 && (uintptr_t)out0 < (uintptr_t)in1) return IVLN_E_INVALID;
+    return IVLN_OK;
+}
+
 // 64 / 32 / 16 lanes per row: 4 / 8 / 16 rows in flight per pass
 template <class Cell>
 int run_cma(const Desc* d, void* stream) {
@@ -433,13 +444,14 @@ int run_cma(const Desc* d, void* stream) {
 extern "C" {
 
 int64_t ivln_cma_step_ws_floats(int rows, int L, int P, int H) {
-    // logits (rows*L) + S (rows*L*2P) + gh2 (rows*3H) + c2 (rows*H) + 16 floats for {barrier counter, error word}
+    // logits (rows*L) + S (rows*L*2P) + gh2 (rows*3H) + c2 (rows*H), each region in whole 128-byte lines
     return al32((int64_t)rows * L) + al32((int64_t)rows * L * 2 * P) + al32((int64_t)rows * 3 * H) + al32((int64_t)rows * H);
 }
 
 int ivln_cma_step_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
     (void)mode;
-    const int rc = check_desc(d);
+    int rc = check_desc(d);
+    if (rc == IVLN_OK) rc = check_state(d, (int64_t)2 * d->H);
     return rc != IVLN_OK ? rc : run_cma<GruCell>(d, stream);
 }
 
@@ -450,16 +462,11 @@ int64_t ivln_cma_step_lstm_ws_floats(int rows, int L, int P, int H) {
 
 int ivln_cma_step_lstm_fwd(const ivln_cma_step_desc* d, int mode, void* stream) {
     (void)mode;
-    const int rc = check_desc(d);
+    int rc = check_desc(d);
     if (rc != IVLN_OK) return rc;
-    if (d->H <= 0 || (d->ld_ho & 3)) return IVLN_E_UNSUPPORTED;
-    // every workgroup reads whole rows of h_in while others write h_out: the (rows, 4, H) views must not share memory
-    const int64_t G = (int64_t)4 * d->H;
-    if (d->ld_h < G || d->ld_ho < G) return IVLN_E_INVALID;
-    const float *in0 = d->h_in, *in1 = d->h_in + (int64_t)(d->rows - 1) * d->ld_h + G;
-    const float *out0 = d->h_out, *out1 = d->h_out + (int64_t)(d->rows - 1) * d->ld_ho + G;
-    if ((uintptr_t)in0 < (uintptr_t)out1 && (uintptr_t)out0 < (uintptr_t)in1) return IVLN_E_INVALID;
-    return run_cma<LstmCell>(d, stream);
+    if (d->ld_ho & 3) return IVLN_E_UNSUPPORTED;
+    rc = check_state(d, (int64_t)4 * d->H);
+    return rc != IVLN_OK ? rc : run_cma<LstmCell>(d, stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ import re
 import pytest
 import torch
 
+from cma_step_ref import FULL, SMALL, make_case
 from lstm_state_ref import MapCMAPolicyLSTMRef, make_policy
 
 pytestmark = pytest.mark.gpu
@@ -122,76 +123,12 @@ def test_gru_policy_is_untouched_by_an_lstm_policy_in_the_same_process(monkeypat
 # ------------------------------------------------------------------------------------------------------------------
 # a. the kernel alone
 # ------------------------------------------------------------------------------------------------------------------
-SMALL = dict(H=64, Hq=32, Ct=16, d_out=16, m_out=32, E=4)
-FULL = dict(H=512, Hq=256, Ct=256, d_out=128, m_out=256, E=32)
 PAD = 8  # floats between two rows of a state view: ld = 4H + 8
 
 
 def _make_case(rows, L, P, w, mask0, seed):
-    """Inputs (fp32, CPU) and the float64 restatement of the head from unfolded weights."""
-    H, Hq, Ct, d_out, m_out, E = (w[k] for k in ("H", "Hq", "Ct", "d_out", "m_out", "E"))
-    sin_w, x2w = d_out + m_out + E, H + Ct + d_out + m_out + E
-    g = torch.Generator().manual_seed(seed)
-    rn = lambda *s, k=1.0: torch.randn(*s, generator=g) * k  # noqa: E731
-    c = dict(rows=rows, L=L, P=P, sin_w=sin_w, x2w=x2w, **w)
-    c["state_in"] = rn(rows, sin_w)
-    c["state"] = torch.stack([rn(rows, H, k=0.5), rn(rows, H), rn(rows, H, k=0.5), rn(rows, H)], 1)  # h1 c1 h2 c2
-    mask = torch.ones(rows, dtype=torch.uint8)
-    mask[0] = mask0  # (rows > 1: an episode starts in row 0, whose incoming h AND c are non-zero)
-    c["mask"] = mask
-    lengths = torch.randint(1, L + 1, (rows,), generator=g).to(torch.int32)
-    if L > 1 and rows > 1:
-        lengths[1 % rows], lengths[2 % rows] = 1, L  # one row of one token, one of the full axis
-    elif L > 1:
-        lengths[0] = L
-    c["lengths"] = lengths
-    txt = rn(rows, Ct, L)
-    txt = txt * (torch.arange(L).view(1, 1, L) < lengths.view(rows, 1, 1))  # the instruction encoder's output is 0 past the end
-    c["txt"] = txt
-    c["dkv"], c["mkv"] = rn(rows, Hq + d_out, P), rn(rows, Hq + m_out, P)
-    c["prev"] = rn(rows, E)
-    for n, I in (("1", sin_w), ("2", H)):
-        c["w_ih" + n], c["b_ih" + n] = rn(4 * H, I, k=0.7 / I ** 0.5), rn(4 * H, k=0.1)
-        c["w_hh" + n], c["b_hh" + n] = rn(4 * H, H, k=0.8 / H ** 0.5), rn(4 * H, k=0.1)
-    c["w_q"], c["b_q"] = rn(Hq, H, k=1.0 / H ** 0.5), rn(Hq, k=0.1)
-    c["w_k"], c["b_k"] = rn(Hq, Ct, k=1.0 / Ct ** 0.5), rn(Hq, k=0.1)
-    c["w_tq"], c["b_tq"] = rn(Hq, Ct, k=1.0 / Ct ** 0.5), rn(Hq, k=0.1)
-    c["w_c"], c["b_c"] = rn(H, x2w, k=1.0 / x2w ** 0.5), rn(H, k=0.1)
-    c["scale"] = float(1.0 / Hq ** 0.5)
-
-    d = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in c.items()}
-    m = mask.double().view(rows, 1)
-
-    def cell(x, h, cs, n):
-        pre = (x @ d["w_ih" + n].t() + d["b_ih" + n]) + ((h * m) @ d["w_hh" + n].t() + d["b_hh" + n])
-        i, f, gg, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
-        ct = f * (cs * m) + i * gg
-        return o * torch.tanh(ct), ct
-
-    def attn(q, k, v, pad=None):
-        lg = torch.einsum("nc,nci->ni", q, k)
-        if pad is not None:
-            lg = lg - pad.double() * 1e8
-        return torch.einsum("ni,nci->nc", torch.softmax(lg * d["scale"], 1), v)
-
-    st = d["state"]
-    h1, c1 = cell(d["state_in"], st[:, 0], st[:, 1], "1")
-    text_k = torch.einsum("qc,nci->nqi", d["w_k"], d["txt"]) + d["b_k"].view(1, Hq, 1)
-    pad = torch.arange(L).view(1, L) >= lengths.view(rows, 1)
-    text = attn(h1 @ d["w_q"].t() + d["b_q"], text_k, d["txt"], pad)
-    q2 = text @ d["w_tq"].t() + d["b_tq"]
-    dep = attn(q2, d["dkv"][:, :Hq], d["dkv"][:, Hq:])
-    mp = attn(q2, d["mkv"][:, :Hq], d["mkv"][:, Hq:])
-    x2 = torch.cat([h1, text, dep, mp, d["prev"]], 1)
-    h2, c2 = cell(torch.relu(x2 @ d["w_c"].t() + d["b_c"]), st[:, 2], st[:, 3], "2")
-    c["ref"] = dict(x2=x2[:, :x2w - E], feats=h2, h1=h1, c1=c1, h2=h2, c2=c2)
-    # the folds the caller supplies, made in float64 and rounded once: [Mq (H + 1 rows) | TQb (Hq rows)] x L per row
-    mq = torch.einsum("qh,nqi->nhi", d["w_q"], text_k)
-    mq_b = torch.einsum("q,nqi->ni", d["b_q"], text_k).view(rows, 1, L)
-    tqb = torch.einsum("qc,nci->nqi", d["w_tq"], d["txt"]) + d["b_tq"].view(1, Hq, 1)
-    c["fold"] = torch.cat([mq, mq_b, tqb], 1).float()
-    c["text_k"] = text_k.float()
-    return c
+    """Inputs (fp32, CPU) and the float64 restatement of the head from unfolded weights (tests/cma_step_ref.py)"""
+    return make_case("lstm", rows, L, P, w, mask0, seed)
 
 
 _cases = {}
