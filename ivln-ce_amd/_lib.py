@@ -52,6 +52,10 @@ def _sig(L):
     L.ivln_mapper_env_counts.argtypes = [vp, i32, C.POINTER(i64), vp]
     L.ivln_mapper_env_export.argtypes = [vp, i32, vp, vp, i64, C.POINTER(i64), vp]
     L.ivln_known_lib_add_from_mapper.argtypes = [vp, i32, vp, i32, vp, i64, vp]
+    # include/ivln_map_seed.h
+    L.ivln_mapper_rows_clear.argtypes = [vp, vp, i32, vp]
+    L.ivln_mapper_env_append.argtypes = [vp, i32, vp, vp, i64, vp]
+    L.ivln_mapper_env_append_from_lib.argtypes = [vp, i32, vp, i32, vp]
 
 
 def lib():

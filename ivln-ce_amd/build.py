@@ -54,6 +54,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_known_lib.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_sizes.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_build.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_map_seed.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

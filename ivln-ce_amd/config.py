@@ -244,6 +244,9 @@ def _experiment_defaults() -> Config:
     # can be captured (mapping.KnownSceneLibrary); False = the copy path (a scene's points are copied into the row's world
     # cloud on every reset and the whole world is compacted every step; eager only)
     _C.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER.known_library = True
+    # prior-map plugins (not a reference key; GTSemanticsPriorMapper / PredictedSemanticsPriorMapper): where a row that
+    # resets reads {env_name}.npz from; "" = the known mappers' locations, data/known_maps/{gt,predicted}_semantics
+    _C.RL.POLICY.OBS_TRANSFORMS.EGOCENTRIC_MAPPER.prior_maps_location = ""
     # --- MODEL (default.py:98-163) ---
     _C.MODEL = CN()
     _C.MODEL.policy_name = "CMAPolicy"

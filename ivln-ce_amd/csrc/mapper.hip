@@ -27,6 +27,7 @@
 #include "../../include/ivln_hip.h"
 #include "../../include/ivln_known_lib.h"
 #include "../../include/ivln_map_build.h"
+#include "../../include/ivln_map_seed.h"
 
 namespace {
 
@@ -835,12 +836,128 @@ __global__ void k_known_entry(KScene* entry, const Pt* rec, int n) {  // (read b
     entry->present = 1;
 }
 
+// ---- seeding an iterative mapper (include/ivln_map_seed.h): rows dropped and pre-built points appended between steps.
+// The cloud is a bag ordered by rank, so "behind the cloud, in front of the next step's local points" is a rank band:
+// residents carry keys < table_cells, a step's local points carry bit 31, appended points take table_cells + a counter
+// of the handle.  What a step reads besides the cloud are the per-env box partials of k_world_select (k_local_argmax folds
+// them into mmWold, the box whose extent gives make_key its multipliers): they stay EXACT - emptied for a dropped row, the
+// exact cell box of the appended points folded into their row's, nothing else touched. ----
+constexpr int kSeedBoxBlocks = 16;  // blocks of box partials a handle gets that has none (never stepped / just reset)
+
+__device__ __forceinline__ void box_store_empty(int* dst4) {
+    *reinterpret_cast<int4*>(dst4) = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
+}
+
+// rows_clear, behind k_known_clear: the partials of every dropped row (keep == 0, or at / beyond B) become empty; the
+// buffers swap as in k_swap_counts (thread 0 writes cnt / cur, which no thread of this launch reads)
+__global__ __launch_bounds__(kThreads) void k_rows_boxes(const uint8_t* __restrict__ keep, int B, Scalars* sc,
+                                                         unsigned capacity, int* __restrict__ bbox, int bbox_B,
+                                                         int bbox_blocks) {
+    const int nb = min(sc->n_bbox, bbox_blocks), ne = min(sc->n_bbox_envs, bbox_B);
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < nb * ne; i += gridDim.x * kThreads) {
+        const int blk = i / ne, e = i - blk * ne;
+        if (e >= B || keep[e] == 0) box_store_empty(bbox + 4 * ((int64_t)blk * bbox_B + e));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int cur = sc->cur & 1;
+        sc->cnt[cur ^ 1] = min(sc->cnt[cur ^ 1], capacity);
+        sc->cnt[cur] = 0;
+        sc->cur = cur ^ 1;
+    }
+}
+
+// append, in front of k_env_append: the partials cover row b.  ONE workgroup (at most 1024 x 64 boxes, usually none): it
+// reads the two scalars, fills, and only then rewrites them - the append kernel behind it reads the new ones.
+//   no partials (n_bbox == 0):  kSeedBoxBlocks blocks x (b + 1) envs, all empty
+//   n_bbox_envs <= b:           columns [n_bbox_envs, b] of every block empty (the row stride is B_max: nothing moves)
+__global__ __launch_bounds__(kThreads) void k_seed_boxes(Scalars* sc, int b, int* __restrict__ bbox, int bbox_B,
+                                                         int bbox_blocks) {
+    int nb = min(sc->n_bbox, bbox_blocks), ne_old = min(sc->n_bbox_envs, bbox_B);
+    if (nb <= 0) {
+        nb = min(kSeedBoxBlocks, bbox_blocks);
+        ne_old = 0;
+    }
+    const int ne = max(ne_old, b + 1), add = ne - ne_old;
+    __syncthreads();  // every thread holds the old scalars
+    for (int i = threadIdx.x; i < nb * add; i += kThreads) {
+        const int blk = i / add, e = ne_old + (i - blk * add);
+        box_store_empty(bbox + 4 * ((int64_t)blk * bbox_B + e));
+    }
+    if (threadIdx.x == 0) {
+        sc->n_bbox = nb;
+        sc->n_bbox_envs = ne;
+    }
+}
+
+// n points -> row b of the source buffer, rank = rank_base + index in the given order.  REC: the library's 16-byte records
+// (one global_load_dwordx4 per point), else xyz f32 (n, 3) + sem u8 (n).  One point per thread and pass, one slot claim per
+// workgroup and pass (wave_append), the workgroup's cell box in LDS behind filtered integer atomics and folded into ONE
+// of row b's partials with four integer atomics at the end: any order of them gives the same box.  (The host checked the
+// capacity and the rank band; wave_append's own check still keeps every store inside the buffer.)
+template <bool REC>
+__global__ __launch_bounds__(kThreads) void k_env_append(const float* __restrict__ xyz, const uint8_t* __restrict__ semv,
+                                                         const KScene* __restrict__ entry, int64_t n, int b,
+                                                         int64_t rank_base, float half_res, Scalars* sc, Pt* w0, Pt* w1,
+                                                         int64_t* r0, int64_t* r1, unsigned capacity,
+                                                         int* __restrict__ bbox, int bbox_B, int bbox_blocks) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4* GlobalRec;
+    __shared__ int box[4];
+    if (threadIdx.x < 4) box[threadIdx.x] = (threadIdx.x & 2) ? INT32_MIN : INT32_MAX;
+    __syncthreads();
+    const int cur = sc->cur & 1;
+    Pt* wsrc = cur ? w1 : w0;
+    int64_t* rsrc = cur ? r1 : r0;
+    GlobalRec rec = nullptr;
+    if (REC) {
+        rec = (GlobalRec)(uintptr_t)entry->rec;
+        n = min(n, (int64_t)entry->n);  // (the host's count of the scene; never past the records)
+    }
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    const int64_t iters = (n + stride - 1) / stride;
+    for (int64_t it = 0; it < iters; ++it) {
+        const int64_t i = it * stride + (int64_t)blockIdx.x * kThreads + threadIdx.x;
+        const bool in = i < n;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (in) {
+            if (REC) {
+                v = rec[i];
+                v.w &= 0xFFu;
+            } else {
+                v.x = __float_as_uint(xyz[3 * i]); v.y = __float_as_uint(xyz[3 * i + 1]); v.z = __float_as_uint(xyz[3 * i + 2]);
+                v.w = semv[i];
+            }
+            v.w |= (uint32_t)b << 8;
+        }
+        const unsigned slot = wave_append(in, &sc->cnt[cur], capacity, &sc->err);
+        if (in && slot != 0xFFFFFFFFu) {
+            *reinterpret_cast<u32x4*>(wsrc + slot) = v;  // one 16-byte store
+            rsrc[slot] = rank_base + i;
+            const int r = cell_index(__uint_as_float(v.z), half_res), c = cell_index(__uint_as_float(v.x), half_res);
+            if (r < box[0]) atomicMin(&box[0], r);
+            if (c < box[1]) atomicMin(&box[1], c);
+            if (r > box[2]) atomicMax(&box[2], r);
+            if (c > box[3]) atomicMax(&box[3], c);
+        }
+    }
+    __syncthreads();
+    const int nb = min(sc->n_bbox, bbox_blocks);  // > 0 and b < n_bbox_envs: k_seed_boxes
+    if (threadIdx.x == 0 && nb > 0 && box[0] <= box[2]) {
+        int* dst = bbox + 4 * ((int64_t)(blockIdx.x % (unsigned)nb) * bbox_B + b);
+        atomicMin(dst + 0, box[0]);
+        atomicMin(dst + 1, box[1]);
+        atomicMax(dst + 2, box[2]);
+        atomicMax(dst + 3, box[3]);
+    }
+}
+
 }  // namespace
 
 struct ivln_known_lib {
     int max_scenes, n_added;
     KScene* table;  // device, fixed for the life of the library
     uint8_t* added;  // host: scene indices that have an entry
+    int64_t* count;  // host: points of each such scene (ivln_mapper_env_append_from_lib sizes its launch by it)
 };
 
 struct ivln_mapper {
@@ -859,6 +976,7 @@ struct ivln_mapper {
     int n_blocks_local;
     int local_blocks, world_blocks;  // launch width of the local- / world-cloud kernels (0: full width)
     int64_t known_rank;
+    int64_t seed_rank;  // appended points so far (include/ivln_map_seed.h): the next one's rank is table_cells + this
     // library-mode known steps (include/ivln_known_lib.h); allocated by ivln_mapper_known_attach
     const ivln_known_lib* klib;
     int* kcur;          // latched scene index per row (-1: none)
@@ -924,6 +1042,7 @@ int ivln_mapper_create(int B_max, int H, int W, double vfov_rad, double height_m
     m->table_cells = table_cells > 0 ? table_cells : (int64_t)(16 << 20);
     if (m->table_cells > (1ll << 31)) m->table_cells = 1ll << 31;  // ranks = keys must fit 31 bits (k_world_max)
     m->known_rank = 0;
+    m->seed_rank = 0;
     m->klib = nullptr; m->kcur = nullptr; m->krot = nullptr; m->kcount = nullptr;
     m->env_part = nullptr; m->env_part_host = nullptr; m->scan_buf = nullptr;
     m->local_blocks = m->world_blocks = 0;
@@ -993,6 +1112,7 @@ int ivln_mapper_destroy(ivln_mapper* m) {
 int ivln_mapper_reset(ivln_mapper* m, void* stream) {
     if (!m) return IVLN_E_INVALID;
     m->known_rank = 0;
+    m->seed_rank = 0;
     if (m->kcur) HIPCHK(hipMemsetAsync(m->kcur, 0xFF, sizeof(int) * (size_t)m->B_max, (hipStream_t)stream));  // -1: no scene
     return init_scalars(m, (hipStream_t)stream);
 }
@@ -1147,7 +1267,8 @@ int ivln_known_lib_create(int max_scenes, ivln_known_lib** out) {
     lib->n_added = 0;
     lib->table = nullptr;
     lib->added = (uint8_t*)calloc((size_t)max_scenes, 1);
-    if (!lib->added || hipMalloc(&lib->table, sizeof(KScene) * (size_t)max_scenes) != hipSuccess ||
+    lib->count = (int64_t*)calloc((size_t)max_scenes, sizeof(int64_t));
+    if (!lib->added || !lib->count || hipMalloc(&lib->table, sizeof(KScene) * (size_t)max_scenes) != hipSuccess ||
         hipMemset(lib->table, 0, sizeof(KScene) * (size_t)max_scenes) != hipSuccess) {
         ivln_known_lib_destroy(lib);
         return IVLN_E_HIP;
@@ -1160,6 +1281,7 @@ int ivln_known_lib_destroy(ivln_known_lib* lib) {
     if (!lib) return IVLN_OK;
     if (lib->table) (void)hipFree(lib->table);
     free(lib->added);
+    free(lib->count);
     delete lib;
     return IVLN_OK;
 }
@@ -1175,6 +1297,7 @@ int ivln_known_lib_add(ivln_known_lib* lib, int scene, const float* xyz, const u
                        lib->table + scene);
     if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
     lib->added[scene] = 1;
+    lib->count[scene] = n;
     lib->n_added += 1;
     return IVLN_OK;
 }
@@ -1392,8 +1515,68 @@ int ivln_known_lib_add_from_mapper(ivln_known_lib* lib, int scene, ivln_mapper* 
                        (int)st[b].n);
     if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
     lib->added[scene] = 1;
+    lib->count[scene] = st[b].n;
     lib->n_added += 1;
     return IVLN_OK;
 }
 
+// ---- seeding an iterative mapper (include/ivln_map_seed.h) ----
+static int seed_refused(const ivln_mapper* m) {
+    return (m->klib || m->known_rank != 0) ? IVLN_E_UNSUPPORTED : IVLN_OK;
+}
+
+int ivln_mapper_rows_clear(ivln_mapper* m, const uint8_t* keep, int B, void* stream) {
+    if (!m || !keep || B <= 0 || B > m->B_max) return IVLN_E_INVALID;
+    const int rc = seed_refused(m);
+    if (rc != IVLN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned cap = (unsigned)m->capacity;
+    hipLaunchKernelGGL(k_known_clear, dim3(256), dim3(kThreads), 0, s, m->wbuf[0], m->wbuf[1], m->rbuf[0], m->rbuf[1], B,
+                       keep, m->sc, cap);
+    hipLaunchKernelGGL(k_rows_boxes, dim3(kSeedBoxBlocks), dim3(kThreads), 0, s, keep, B, m->sc, cap, m->bbox, m->B_max,
+                       kWorldBlocks);
+    return hipGetLastError() == hipSuccess ? IVLN_OK : IVLN_E_HIP;
+}
+
+// the checks that need the device (arguments were checked by the caller), then the two launches
+static int env_append(ivln_mapper* m, int b, const float* xyz, const uint8_t* sem, const KScene* entry, int64_t n,
+                      hipStream_t s) {
+    const int64_t rank_base = m->table_cells + m->seed_rank;
+    if (n > (1ll << 31) - rank_base) return IVLN_E_KEYSPACE;
+    if (n == 0) return IVLN_OK;
+    Scalars h;
+    HIPCHK(hipMemcpyAsync(&h, m->sc, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((int64_t)h.cnt[h.cur & 1] + n > m->capacity) return IVLN_E_CAPACITY;
+    hipLaunchKernelGGL(k_seed_boxes, dim3(1), dim3(kThreads), 0, s, m->sc, b, m->bbox, m->B_max, kWorldBlocks);
+    int blocks = (int)((n + kThreads - 1) / kThreads);
+    if (blocks > kWorldBlocks) blocks = kWorldBlocks;
+    const unsigned cap = (unsigned)m->capacity;
+    if (entry)
+        hipLaunchKernelGGL(k_env_append<true>, dim3(blocks), dim3(kThreads), 0, s, (const float*)nullptr,
+                           (const uint8_t*)nullptr, entry, n, b, rank_base, m->half_res, m->sc, m->wbuf[0], m->wbuf[1],
+                           m->rbuf[0], m->rbuf[1], cap, m->bbox, m->B_max, kWorldBlocks);
+    else
+        hipLaunchKernelGGL(k_env_append<false>, dim3(blocks), dim3(kThreads), 0, s, xyz, sem, (const KScene*)nullptr, n, b,
+                           rank_base, m->half_res, m->sc, m->wbuf[0], m->wbuf[1], m->rbuf[0], m->rbuf[1], cap, m->bbox,
+                           m->B_max, kWorldBlocks);
+    if (hipGetLastError() != hipSuccess) return IVLN_E_HIP;
+    m->seed_rank += n;
+    return IVLN_OK;
+}
+
+int ivln_mapper_env_append(ivln_mapper* m, int b, const float* xyz, const uint8_t* sem, int64_t n, void* stream) {
+    if (!m || b < 0 || b >= m->B_max || n < 0 || (n > 0 && (!xyz || !sem))) return IVLN_E_INVALID;
+    const int rc = seed_refused(m);
+    if (rc != IVLN_OK) return rc;
+    return env_append(m, b, xyz, sem, nullptr, n, (hipStream_t)stream);
+}
+
+int ivln_mapper_env_append_from_lib(ivln_mapper* m, int b, const ivln_known_lib* lib, int scene, void* stream) {
+    if (!m || b < 0 || b >= m->B_max || !lib || scene < 0 || scene >= lib->max_scenes || !lib->added[scene])
+        return IVLN_E_INVALID;
+    const int rc = seed_refused(m);
+    if (rc != IVLN_OK) return rc;
+    return env_append(m, b, nullptr, nullptr, lib->table + scene, lib->count[scene], (hipStream_t)stream);
+}
 }  // extern "C"

@@ -525,6 +525,122 @@ class MappingModule:
               "ivln_mapper_env_export")
         return xyz[:n].cpu().numpy(), sem[:n].cpu().numpy()
 
+    # -- seeding (include/ivln_map_seed.h): rows dropped / pre-built points appended between steps; save and restore --------
+    def ensure_handle(self, H: int, W: int):
+        """Creates the C handle for H x W depth frames if the module has none for that size yet (a step does the same)."""
+        self._ensure_handle(int(H), int(W))
+
+    def _seedable(self, what):
+        if self.mode != "iterative":
+            raise _lib.IvlnError(f"MappingModule.{what}: iterative mode only")
+        if self._begin_open:
+            raise _lib.IvlnError(f"MappingModule.{what}: `begin` is open - the cloud is defined between complete steps only")
+        if self._h is None:
+            raise _lib.IvlnError(f"MappingModule.{what}: no handle yet - run a step or call ensure_handle(H, W) first")
+
+    def _c_rows_clear(self, keep, B):
+        """The C call (tests replace it with a stub)."""
+        check(lib().ivln_mapper_rows_clear(self._h, dptr(keep), int(B), stream_ptr()), "ivln_mapper_rows_clear")
+
+    def _c_append(self, b, xyz, sem):
+        """The C call (tests replace it with a stub): xyz (n, 3) f32 and sem (n,) u8, contiguous on the device."""
+        check(lib().ivln_mapper_env_append(self._h, int(b), xyz.data_ptr(), sem.data_ptr(), xyz.shape[0], stream_ptr()),
+              "ivln_mapper_env_append")
+
+    def _c_append_from_lib(self, b, library, scene):
+        check(lib().ivln_mapper_env_append_from_lib(self._h, int(b), library.handle(), int(scene), stream_ptr()),
+              "ivln_mapper_env_append_from_lib")
+
+    def clear_rows(self, keep):
+        """Drops the cloud of every row b with keep[b] == 0 and of every row >= len(keep) - what a step does with
+        `not_done_masks` (mapper.py:310-326), on its own."""
+        self._seedable("clear_rows")
+        keep = torch.as_tensor(keep).reshape(-1).to(self.device, torch.uint8).contiguous()
+        if not 1 <= keep.shape[0] <= self.b_max:
+            raise _lib.IvlnError(f"clear_rows: {keep.shape[0]} rows outside [1, {self.b_max}]")
+        self._c_rows_clear(keep, keep.shape[0])
+
+    def _row_arrays(self, what, b, xyz, sem):
+        if not 0 <= int(b) < self.b_max:
+            raise _lib.IvlnError(f"{what}: row {b} outside [0, {self.b_max})")
+        xyz = torch.as_tensor(xyz).to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        sem = torch.as_tensor(sem).reshape(-1).to(self.device, torch.uint8).contiguous()
+        if xyz.shape[0] != sem.shape[0]:
+            raise ValueError(f"{what}: {xyz.shape[0]} points but {sem.shape[0]} labels")
+        return xyz, sem
+
+    def seed_row(self, b: int, xyz, sem):
+        """Appends a pre-built cloud - xyz (n, 3) float32, semantics (n,) uint8, the arrays of a known-map file - to row b:
+        behind every point of the cloud, in the given order, in front of the next step's points (mapper.py:871-879)."""
+        self._seedable("seed_row")
+        xyz, sem = self._row_arrays("seed_row", b, xyz, sem)
+        self._c_append(b, xyz, sem)
+
+    def seed_row_from_library(self, b: int, library: KnownSceneLibrary, name: str):
+        """`seed_row` with scene `name` of a device-resident library (read from its file on first sight): no host copy."""
+        self._seedable("seed_row_from_library")
+        if not 0 <= int(b) < self.b_max:
+            raise _lib.IvlnError(f"seed_row_from_library: row {b} outside [0, {self.b_max})")
+        self._c_append_from_lib(b, library, library.index(name))
+
+    def _geometry(self):
+        md = self.map_dimensions
+        return {"rows": md.num_rows, "cols": md.num_cols, "resolution_meters": float(md.resolution_meters),
+                "frame_size": list(self._hw) if self._hw is not None else None, "b_max": int(self.b_max)}
+
+    def state_dict(self):
+        """The mapper's state between two steps: the geometry it was taken with (rows, cols, resolution_meters, frame_size
+        [H, W], b_max) and the world cloud in ascending rank - xyz (n, 3) float32, batch (n,) int32, semantics (n,) uint8,
+        CPU tensors, so the dict goes through torch.save / torch.load.  Built from ivln_mapper_world_export."""
+        self._exportable("state_dict")
+        xyz, batch, sem = self.world_cloud()
+        sd = self._geometry()
+        sd.update(xyz=torch.from_numpy(np.ascontiguousarray(xyz)), batch=torch.from_numpy(np.ascontiguousarray(batch)),
+                  semantics=torch.from_numpy(np.ascontiguousarray(sem)))
+        return sd
+
+    def load_state_dict(self, sd):
+        """Resets the mapper and appends the saved cloud run by run - a run is a stretch of consecutive points of one row
+        in rank order (one per row, more only where quirk Q2 interleaves rows).  Appends keep call order, so the restored
+        cloud has the saved order exactly and every later step equals the uninterrupted mapper's.  A state taken with
+        another map geometry or frame size raises ValueError naming both; nothing is touched then."""
+        if self.mode != "iterative":
+            raise _lib.IvlnError("MappingModule.load_state_dict: iterative mode only")
+        if self._begin_open:
+            raise _lib.IvlnError("MappingModule.load_state_dict: `begin` is open")
+        mine = self._geometry()
+        if mine["frame_size"] is None and self.camera_parameters is not None:
+            mine["frame_size"] = [int(v) for v in self.camera_parameters.features_spatial_dimensions]
+        theirs = {k: sd[k] for k in ("rows", "cols", "resolution_meters", "frame_size")}
+        theirs["frame_size"] = [int(v) for v in theirs["frame_size"]]
+        for k, v in theirs.items():
+            if mine[k] is not None and mine[k] != v:
+                raise ValueError(f"mapper state was taken with {k} = {v}, this mapper has {k} = {mine[k]}")
+        xyz, batch, sem = sd["xyz"], torch.as_tensor(sd["batch"]).reshape(-1), sd["semantics"]
+        n = int(batch.shape[0])
+        if tuple(xyz.shape) != (n, 3) or tuple(sem.shape) != (n,):
+            raise ValueError(f"mapper state: xyz {tuple(xyz.shape)}, batch ({n},), semantics {tuple(sem.shape)} do not match")
+        if n and not (0 <= int(batch.min()) and int(batch.max()) < self.b_max):
+            raise ValueError(f"mapper state holds rows up to {int(batch.max())}, this mapper has b_max = {self.b_max}")
+        runs = cloud_runs(batch)
+        self._ensure_handle(*theirs["frame_size"])
+        self.reset()
+        xyz = xyz.to(self.device, torch.float32).contiguous()
+        sem = sem.to(self.device, torch.uint8).contiguous()
+        for b, lo, hi in runs:
+            self._c_append(b, xyz[lo:hi], sem[lo:hi])
+
+
+def cloud_runs(batch):
+    """Stretches of consecutive equal entries of `batch` (n,): [(row, start, stop)], in order."""
+    batch = np.asarray(torch.as_tensor(batch).cpu()).reshape(-1)
+    if batch.shape[0] == 0:
+        return []
+    cuts = np.flatnonzero(batch[1:] != batch[:-1]) + 1
+    starts = np.concatenate(([0], cuts))
+    stops = np.concatenate((cuts, [batch.shape[0]]))
+    return [(int(batch[s]), int(s), int(e)) for s, e in zip(starts, stops)]
+
 
 def create_gt_semantics_iterative_mapper(device, camera_parameters, map_dimensions, **kw) -> MappingModule:
     """mapper.py:991-998."""

@@ -1,12 +1,15 @@
 """Observation-transformer plugins with the reference's registry names
 (ivlnce_baselines/common/obs_transforms.py:30-176): `GTSemanticsIterativeMapper`,
-`PredictedSemanticsIterativeMapper`, `GTSemanticsKnownMapper`, `PredictedSemanticsKnownMapper`.
+`PredictedSemanticsIterativeMapper`, `GTSemanticsKnownMapper`, `PredictedSemanticsKnownMapper` - and, not in the
+reference, `GTSemanticsPriorMapper` / `PredictedSemanticsPriorMapper`: iterative mappers whose rows start from a known map.
 Same constructor, `from_config`, `transform_observation_space` and `forward(dict) -> dict`
 behaviour; the map arithmetic runs in the HIP mapper (csrc/mapper.hip)."""
 import math
+import os
 from typing import Dict
 
 import numpy as np
+import torch
 import torch.nn as nn
 from torch import Tensor
 
@@ -19,6 +22,7 @@ from .mapping import (
     create_predicted_semantics_known_mapper,
     extract_camera_parameters,
     extract_egocentric_map_parameters,
+    load_known_scene,
 )
 from .registry import baseline_registry
 from .spaces import Box
@@ -130,6 +134,7 @@ class Mapper(ObservationTransformer):
         tr.sizing = {k: int(getattr(mp, k)) for k in ("table_cells", "world_capacity") if int(getattr(mp, k, 0) or 0) > 0}
         tr.sizing["b_max"] = 64  # envs per process the mapper is sized for (ivln_mapper_create: <= 64)
         tr.known_library = bool(getattr(mp, "known_library", True))  # (read by the known-map plugins only)
+        tr.prior_maps_location = str(getattr(mp, "prior_maps_location", "") or "")  # (read by the prior-map plugins only)
         return tr
 
 
@@ -189,6 +194,81 @@ class GTSemanticsKnownMapper(_KnownMapper):
 @baseline_registry.register_obs_transformer()
 class PredictedSemanticsKnownMapper(_KnownMapper):
     _factory = staticmethod(create_predicted_semantics_known_mapper)
+
+
+class _PriorMapper(Mapper):
+    """Prior-map plugins: an iterative mapper whose row, when its map resets (`not_done_masks[b] == 0`), starts from
+    `{maps_location}/{env_name}.npz` - the files of known-map mode, which `known_maps.build_known_maps` writes - instead of
+    empty, and keeps mapping on top of it (include/ivln_map_seed.h).  One step: read `not_done` (one device-to-host read,
+    as the known mappers' copy path does), drop the cleared rows, seed each reset row in batch order from a per-scene
+    device cache, run the ordinary iterative step with `not_done` 1 on the seeded rows.  The reset path reads the host, so
+    these steps stay eager (trainers._graph_eligible goes by the class name)."""
+
+    prior_maps_location = ""  # "" = the known mappers' default location (from_config: EGOCENTRIC_MAPPER.prior_maps_location)
+    _default_location = None
+    _factory = None
+
+    @property
+    def maps_location(self):
+        return self.prior_maps_location or type(self)._default_location
+
+    def setup_mapping_module(self, observations):
+        if self.mapping_module is None:
+            self.mapping_module = type(self)._factory(
+                device=observations["depth"].device, camera_parameters=self.camera_parameters,
+                map_dimensions=self.map_dimensions, **self.sizing
+            )
+            self._scenes = {}  # env_name -> (xyz, semantics) on the device
+
+    def _scene(self, name):
+        if name not in self._scenes:
+            xyz, sem = load_known_scene(self.maps_location, name)
+            dev = self.mapping_module.device
+            self._scenes[name] = (torch.from_numpy(xyz).to(dev), torch.from_numpy(sem).to(dev))
+        return self._scenes[name]
+
+    def update_maps_from_observations(self, observations):
+        mm = self.mapping_module
+        depth = observations["depth"]
+        B = depth.shape[0]
+        not_done = observations["not_done_masks"].reshape(-1).to(torch.uint8).contiguous()
+        reset = np.flatnonzero(not_done.cpu().numpy() == 0).tolist()
+        names = [str(observations["env_name"][b]) for b in reset]
+        for name in names:  # before any device work of the step
+            path = os.path.join(self.maps_location, f"{name}.npz")
+            if name not in self._scenes and not os.path.isfile(path):
+                raise FileNotFoundError(f"prior map {path} not found (scene {name!r})")
+        if B > mm.b_max:
+            raise ValueError(f"batch {B} > b_max {mm.b_max}")
+        mm.ensure_handle(depth.shape[1], depth.shape[2])
+        mm.clear_rows(not_done)
+        for b, name in zip(reset, names):
+            mm.seed_row(b, *self._scene(name))
+        obs = dict(observations)  # (the caller's masks stay what they are: the policy reads them)
+        # every row is now either one whose not_done was non-zero already or a seeded one, which keeps its seed
+        obs["not_done_masks"] = torch.ones((B, 1), dtype=torch.uint8, device=not_done.device)
+        mem = mm(obs)
+        observations["occupancy_map"] = mem.occupancy
+        observations["semantic_map"] = mem.semantic
+        return observations
+
+    def begin_maps(self, observations):
+        raise NotImplementedError("prior-map plugins step eagerly (the reset path reads the host): use forward")
+
+    finish_maps = begin_maps
+
+
+@baseline_registry.register_obs_transformer()
+class GTSemanticsPriorMapper(_PriorMapper):
+    _default_location = "data/known_maps/gt_semantics"
+    _factory = staticmethod(create_gt_semantics_iterative_mapper)
+
+
+@baseline_registry.register_obs_transformer()
+class PredictedSemanticsPriorMapper(_PriorMapper):
+    predicted_semantics = True  # (as PredictedSemanticsIterativeMapper)
+    _default_location = "data/known_maps/predicted_semantics"
+    _factory = staticmethod(create_predicted_semantics_iterative_mapper)
 
 
 def get_active_obs_transforms(config):
