@@ -30,6 +30,7 @@ SOURCES = {
     "train_ops.hip": [],
     "depth_bwd.hip": [],
     "rgb_bwd.hip": [],
+    "seg_loss.hip": [],
     "dtw.cpp": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -55,6 +56,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_sizes.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_build.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_seed.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_seg_train.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

@@ -19,7 +19,7 @@ from . import ops
 from .aux_losses import AuxLosses
 from .encoders import InstructionEncoder, VlnResnetDepthEncoder, build_rnn_state_encoder
 from .policy import ILPolicy, Net
-from .rednet import Bottleneck, _Folded
+from .rednet import Bottleneck, _Folded, _bottleneck_train, _conv_bn_train  # noqa: F401  (the train-mode layer helpers live beside Bottleneck)
 from .registry import baseline_registry
 
 
@@ -141,49 +141,6 @@ class _ResNet50Body(nn.Sequential):
         self.full_output = out
         self._epoch = -1  # (the running statistics moved: `forward` folds them again)
         return out[:, :c]
-
-
-def _conv_bn_train(x, conv, bn):
-    """conv -> the BatchNorm's scale / shift, not applied yet: (dict(raw, train[, mean, rstd]), scale, shift).  Train mode:
-    batch statistics, mean / rstd kept for the backward, running statistics and num_batches_tracked updated; eval mode:
-    the running statistics (the backward reads them from the module: dx = gamma * rstd * dz)."""
-    C = bn.num_features
-    scale = torch.empty(C, dtype=torch.float32, device=x.device)
-    shift = torch.empty(C, dtype=torch.float32, device=x.device)
-    if not bn.training:
-        raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0])
-        ops.bn_fold(bn, scale, shift)
-        return dict(raw=raw, train=False), scale, shift
-    stats = [] if ops.CONV_STATS else None
-    raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0], stats=stats)
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    if stats:
-        ops.bn_stats_from_partials(stats[0][0], stats[0][1], bn, scale, shift, mean, rstd)
-    else:  # (the launch left no per-tile statistics - split K, a kernel without that epilogue: from the output)
-        ops.bn_train_stats(raw, bn, scale, shift, mean, rstd)
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked += 1
-    return dict(raw=raw, mean=mean, rstd=rstd, train=True), scale, shift
-
-
-def _bottleneck_train(blk: Bottleneck, x, save):
-    """Bottleneck.forward_hip for the differentiated pass.  Appends dict(x, l1, l2, l3, ds | None, out) to `save`; l1 / l2 =
-    dict(raw, out, ...) of a conv -> BatchNorm -> ReLU layer, l3 / ds = dict(raw, ...) of the two BatchNorms that meet in the
-    tail out = relu(bn3(c3) + bn_ds(ds) | x), one launch."""
-    l1, s, b = _conv_bn_train(x, blk.conv1, blk.bn1)
-    l1["out"] = ops.bn_apply(l1["raw"], s, b, relu=True)
-    l2, s, b = _conv_bn_train(l1["out"], blk.conv2, blk.bn2)
-    l2["out"] = ops.bn_apply(l2["raw"], s, b, relu=True)
-    l3, s, b = _conv_bn_train(l2["out"], blk.conv3, blk.bn3)
-    ds = None
-    if blk.downsample is not None:
-        ds, sd, bd = _conv_bn_train(x, blk.downsample[0], blk.downsample[1])
-        out = ops.bn_apply(l3["raw"], s, b, relu=True, x2=ds["raw"], scale2=sd, shift2=bd)
-    else:
-        out = ops.bn_apply(l3["raw"], s, b, relu=True, residual=x)
-    save.append(dict(x=x, l1=l1, l2=l2, l3=l3, ds=ds, out=out))
-    return out
 
 
 class LatentCMANet(Net):

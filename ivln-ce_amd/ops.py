@@ -2276,6 +2276,77 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.9
     )
 
 
+# ---- segmentation loss and metrics (include/ivln_seg_train.h, csrc/seg_loss.hip) ------------------------
+_seg_state = {}
+
+
+def _seg_ws(device):
+    """(double workspace, the sticky int32 error word) of the current (device, stream)."""
+    key = (str(device), stream_ptr())
+    st = _seg_state.get(key)
+    if st is None:
+        st = _seg_state[key] = (torch.empty(2064, dtype=torch.float64, device=device),
+                                torch.zeros(1, dtype=torch.int32, device=device))
+    return st
+
+
+def seg_check(device, what="segmentation labels"):
+    """Reads the error word of the segmentation kernels (synchronises); set: clears it and raises - the launches that saw it
+    set wrote nothing."""
+    _, err = _seg_ws(device)
+    if int(err.item()) != 0:
+        err.zero_()
+        raise _lib.IvlnError(f"{what}: a label outside [0, classes) that is not the ignore label (nothing was written)")
+
+
+def seg_ce(scores, labels_u8, stride=1, class_weights=None, ignore_label=None, scale=1.0, loss=None, dscores=None,
+           want_grad=True, check_labels=True):
+    """Pixel cross-entropy of NCHW scores (N, C, h, w) against u8 labels (N, h * stride, w * stride) read at every
+    stride-th pixel: F.cross_entropy(weight=, ignore_index=, reduction="mean") -> (loss (1,) device tensor, dscores = scale *
+    d loss / d scores | None).  Every pixel ignored: loss 0, gradient 0 (torch: NaN).  check_labels: read the error word back
+    (one synchronisation) and raise on an out-of-range label; False leaves that to a later seg_check()."""
+    N, Cc, h, w = scores.shape
+    if (labels_u8.dtype != torch.uint8 or labels_u8.numel() != N * h * stride * w * stride or stride < 1
+            or tuple(labels_u8.shape[:3]) != (N, h * stride, w * stride)):
+        raise _lib.IvlnError(f"seg_ce: scores {tuple(scores.shape)} at stride {stride} need u8 labels ({N}, {h * stride}, "
+                             f"{w * stride}), got {labels_u8.dtype} {tuple(labels_u8.shape)}")
+    if class_weights is not None and (class_weights.numel() != Cc or class_weights.dtype != torch.float32):
+        raise _lib.IvlnError(f"seg_ce: {Cc} f32 class weights, got {tuple(class_weights.shape)}")
+    dev = scores.device
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    if dscores is None and want_grad:
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=dev)
+    ws, err = _seg_ws(dev)
+    L = _L()
+    L.ivln_seg_ce_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i64, vp, vp]
+    check(L.ivln_seg_ce_f32(dptr(scores), dptr(labels_u8), _p(class_weights.contiguous() if class_weights is not None else None),
+                            N, Cc, h, w, stride, -1 if ignore_label is None else int(ignore_label), float(scale), dptr(loss),
+                            dptr(dscores) if dscores is not None else None, dptr(ws), ws.numel(), dptr(err), stream_ptr()),
+          "ivln_seg_ce_f32")
+    if check_labels:
+        seg_check(dev, "seg_ce")
+    return loss, dscores
+
+
+def seg_confusion(pred_u8, truth_u8, classes, ignore_label=None, counts=None, check_labels=True):
+    """counts[t][p] += pixels with truth t and prediction p, the ignore label skipped -> (classes, classes) int64."""
+    if pred_u8.dtype != torch.uint8 or truth_u8.dtype != torch.uint8 or pred_u8.numel() != truth_u8.numel():
+        raise _lib.IvlnError("seg_confusion: u8 predictions and u8 labels of one size")
+    dev = pred_u8.device
+    if counts is None:
+        counts = torch.zeros((classes, classes), dtype=torch.int64, device=dev)
+    _, err = _seg_ws(dev)
+    L = _L()
+    L.ivln_seg_confusion_u8.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    check(L.ivln_seg_confusion_u8(dptr(pred_u8), dptr(truth_u8), pred_u8.numel(), classes,
+                                  -1 if ignore_label is None else int(ignore_label), dptr(counts), dptr(err), stream_ptr()),
+          "ivln_seg_confusion_u8")
+    if check_labels:
+        seg_check(dev, "seg_confusion")
+    return counts
+
+
 # ---- GEMM-shaped gradients ----------------------------------------------------------------------------
 def linear_bwd_input(dy, w, out=None, accumulate=False, splits=None, info=None):
     """dX[r][i] = sum_o dY[r][o] W[o][i]  (dy, out may be row-strided)."""

@@ -2,10 +2,11 @@
 
 Same module / parameter names as the reference (ivlnce_baselines/common/mapping_module/rednet.py:7-358)
 so `rednet_mp3d_best_model.pkl["model_state"]` loads unchanged; `PredictSemantics` mirrors
-mapper.py:703-800.  Inference only (the reference freezes it and runs it under no_grad in eval
+mapper.py:703-800.  `forward` is inference only (the reference freezes it and runs it under no_grad in eval
 mode): every BatchNorm is folded into the producing conv's fused scale/shift epilogue, residual
 adds and ReLU run in the same GEMM epilogue, transposed convs use the transposed-gather operand
-mode of the MFMA implicit-GEMM kernel.
+mode of the MFMA implicit-GEMM kernel.  Fine-tuning has its own entry point, `RedNet.forward_train` (the reference's
+five-output training pass, every conv output materialised), walked back by train.rednet_backward (rednet_train.py).
 """
 import os
 
@@ -224,6 +225,49 @@ def _bottleneck_pair(blk: Bottleneck, blk_d: Bottleneck, x2, f: _Folded, entry_b
     return _conv_pair(y, w3, s3, b3, residual=residual, relu=True)
 
 
+def _conv_bn_train(x, conv, bn):
+    """conv -> the BatchNorm's scale / shift, not applied yet: (dict(raw, train[, mean, rstd]), scale, shift).  Train mode:
+    batch statistics, mean / rstd kept for the backward, running statistics and num_batches_tracked updated; eval mode:
+    the running statistics (the backward reads them from the module: dx = gamma * rstd * dz)."""
+    C = bn.num_features
+    scale = torch.empty(C, dtype=torch.float32, device=x.device)
+    shift = torch.empty(C, dtype=torch.float32, device=x.device)
+    if not bn.training:
+        raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0])
+        ops.bn_fold(bn, scale, shift)
+        return dict(raw=raw, train=False), scale, shift
+    stats = [] if ops.CONV_STATS else None
+    raw = ops.conv2d(x, conv.weight, stride=conv.stride[0], pad=conv.padding[0], stats=stats)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    if stats:
+        ops.bn_stats_from_partials(stats[0][0], stats[0][1], bn, scale, shift, mean, rstd)
+    else:  # (the launch left no per-tile statistics - split K, a kernel without that epilogue: from the output)
+        ops.bn_train_stats(raw, bn, scale, shift, mean, rstd)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return dict(raw=raw, mean=mean, rstd=rstd, train=True), scale, shift
+
+
+def _bottleneck_train(blk: Bottleneck, x, save):
+    """Bottleneck.forward_hip for the differentiated pass.  Appends dict(x, l1, l2, l3, ds | None, out) to `save`; l1 / l2 =
+    dict(raw, out, ...) of a conv -> BatchNorm -> ReLU layer, l3 / ds = dict(raw, ...) of the two BatchNorms that meet in the
+    tail out = relu(bn3(c3) + bn_ds(ds) | x), one launch."""
+    l1, s, b = _conv_bn_train(x, blk.conv1, blk.bn1)
+    l1["out"] = ops.bn_apply(l1["raw"], s, b, relu=True)
+    l2, s, b = _conv_bn_train(l1["out"], blk.conv2, blk.bn2)
+    l2["out"] = ops.bn_apply(l2["raw"], s, b, relu=True)
+    l3, s, b = _conv_bn_train(l2["out"], blk.conv3, blk.bn3)
+    ds = None
+    if blk.downsample is not None:
+        ds, sd, bd = _conv_bn_train(x, blk.downsample[0], blk.downsample[1])
+        out = ops.bn_apply(l3["raw"], s, b, relu=True, x2=ds["raw"], scale2=sd, shift2=bd)
+    else:
+        out = ops.bn_apply(l3["raw"], s, b, relu=True, residual=x)
+    save.append(dict(x=x, l1=l1, l2=l2, l3=l3, ds=ds, out=out))
+    return out
+
+
 class TransBasicBlock(nn.Module):
     expansion = 1
 
@@ -257,6 +301,58 @@ class TransBasicBlock(nn.Module):
             return _convt(y, self.conv2, f, scale=s, shift=b, residual=residual, relu=True)
         return ops.conv2d(y, self.conv2.weight, stride=self.stride, pad=1, scale=s, shift=b, residual=residual,
                           relu=True)
+
+
+def _convt_bn_train(x, convt: nn.ConvTranspose2d, bn):
+    """_conv_bn_train for a transposed conv: the raw output through the transposed-gather GEMM (no BatchNorm folded in), the
+    train-mode statistics from that output."""
+    C = bn.num_features
+    scale = torch.empty(C, dtype=torch.float32, device=x.device)
+    shift = torch.empty(C, dtype=torch.float32, device=x.device)
+    raw = ops.conv_transpose2d(x, ops.weight_oi_transpose(convt.weight), convt.stride[0], convt.padding[0],
+                               convt.output_padding[0])
+    if not bn.training:
+        ops.bn_fold(bn, scale, shift)
+        return dict(raw=raw, train=False), scale, shift
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    ops.bn_train_stats(raw, bn, scale, shift, mean, rstd)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return dict(raw=raw, mean=mean, rstd=rstd, train=True), scale, shift
+
+
+def _any_conv_bn_train(x, conv, bn):
+    return (_convt_bn_train if isinstance(conv, nn.ConvTranspose2d) else _conv_bn_train)(x, conv, bn)
+
+
+def _transblock_train(blk: TransBasicBlock, x, save):
+    """TransBasicBlock.forward_hip for the differentiated pass.  Appends dict(x, l1, l2, up | None, out) to `save`: l1 =
+    dict(raw, out, ...) of conv1 -> BatchNorm -> ReLU, l2 / up = dict(raw, ...) of the two BatchNorms that meet in the tail
+    out = relu(bn2(c2) + bn_up(up) | x), one launch (train.rednet_backward walks it)."""
+    l1, s, b = _conv_bn_train(x, blk.conv1, blk.bn1)
+    l1["out"] = ops.bn_apply(l1["raw"], s, b, relu=True)
+    l2, s, b = _any_conv_bn_train(l1["out"], blk.conv2, blk.bn2)
+    up = None
+    if blk.upsample is not None:
+        up, su, bu = _any_conv_bn_train(x, blk.upsample[0], blk.upsample[1])
+        out = ops.bn_apply(l2["raw"], s, b, relu=True, x2=up["raw"], scale2=su, shift2=bu)
+    else:
+        out = ops.bn_apply(l2["raw"], s, b, relu=True, residual=x)
+    save.append(dict(x=x, l1=l1, l2=l2, up=up, out=out))
+    return out
+
+
+def _agant_train(layer, x):
+    """An `agant` skip layer (1x1 conv -> BatchNorm -> ReLU) for the differentiated pass: dict(x, raw, out, ...)."""
+    s, sc, sh = _conv_bn_train(x, layer[0], layer[1])
+    s.update(x=x, out=ops.bn_apply(s["raw"], sc, sh, relu=True))
+    return s
+
+
+def _head_train(conv: nn.Conv2d, x):
+    """An auxiliary 1x1 score head with its bias (shift-only epilogue)."""
+    return ops.conv2d(x, conv.weight, shift=conv.bias)
 
 
 class RedNet(nn.Module):
@@ -355,6 +451,105 @@ class RedNet(nn.Module):
         s, b = self._folded.bn(layer[1])
         out = ops.conv2d(fuse, layer[0].weight, scale=s, shift=b, residual=up, relu=True, residual_after_relu=True) if SKIP_ADD_FUSED else None
         return out if out is not None else ops.add(up, self._agant(layer, fuse))
+
+    TRAINABLE = ("all", "decoder")
+
+    def trainable_parameters(self, trainable="all"):
+        """[(name, parameter)] that forward_train / train.rednet_backward train: everything, or - "decoder" - all but the two
+        encoders (the `agant` skips, the decoder, the final transposed conv and the four auxiliary heads)."""
+        if trainable not in self.TRAINABLE:
+            raise ValueError(f"trainable is one of {self.TRAINABLE}, got {trainable!r}")
+        enc = ("conv1.", "bn1.", "conv1_d.", "bn1_d.", "layer")
+        return [(k, p) for k, p in self.named_parameters() if trainable == "all" or not k.startswith(enc)]
+
+    def _encoders_frozen(self, rgb, depth):
+        """The two encoders as `forward` runs them (stacked launches, folded running statistics, no saves) -> [fuse0 .. fuse4].
+        Nothing is differentiated here, so a fusion add may land in place on the RGB half as it does in `forward`."""
+        f = self._folded
+        B = rgb.shape[0]
+        layers = ((self.layer1, self.layer1_d), (self.layer2, self.layer2_d), (self.layer3, self.layer3_d),
+                  (self.layer4, self.layer4_d))
+        s, b = f.bn(self.bn1)
+        sd, bd = f.bn(self.bn1_d)
+        if GROUP_ENCODERS:  # the stacked [RGB ; depth] launches of `forward`: a fusion add in place on the first half
+            S = torch.empty((2 * B, 64, rgb.shape[2] // 2, rgb.shape[3] // 2), dtype=torch.float32, device=rgb.device)
+            ops.conv2d(depth, self.conv1_d.weight, stride=2, pad=3, scale=sd, shift=bd, relu=True, out=S[B:])
+            ops.conv2d(rgb, self.conv1.weight, stride=2, pad=3, scale=s, shift=b, relu=True, out=S[:B])
+            fuses = [ops.add(S[:B], S[B:], out=S[:B])]
+            P = ops.pool2d(S, 3, 2, 1, "max")
+            for la, lb in layers:
+                for blk, blk_d in zip(la, lb):
+                    P = _bottleneck_pair(blk, blk_d, P, f)
+                fuses.append(ops.add(P[:B], P[B:], out=P[:B]))
+            return fuses
+        x = ops.conv2d(rgb, self.conv1.weight, stride=2, pad=3, scale=s, shift=b, relu=True)
+        d = ops.conv2d(depth, self.conv1_d.weight, stride=2, pad=3, scale=sd, shift=bd, relu=True)
+        fuses = [ops.add(x, d)]
+        x, d = ops.pool2d(fuses[0], 3, 2, 1, "max"), ops.pool2d(d, 3, 2, 1, "max")
+        for la, lb in layers:
+            x, d = self._seq(la, x), self._seq(lb, d)
+            fuses.append(ops.add(x, d))
+            x = fuses[-1]
+        return fuses
+
+    def forward_train(self, rgb, depth, save, trainable="all"):
+        """The five-output training pass (rednet.py:224-256 with self.training): rgb (B,3,H,W) / depth (B,1,H,W) normalised as
+        PredictSemantics.scores makes them -> (out, out2, out3, out4, out5) at H, H/2, H/4, H/8, H/16; out5 .. out2 = the
+        auxiliary heads on deconv1 .. deconv4's outputs in front of the skip adds.  Layer by layer, every conv output
+        materialised, no BatchNorm folded into a conv: a BatchNorm module in train mode normalises with the batch statistics and
+        moves its running statistics as torch does, one in eval mode uses the running statistics (train=False in its save).
+        `save` (a dict) receives what train.rednet_backward walks.  trainable="decoder": the two encoders run the frozen
+        forward (`_encoders_frozen`: folded running statistics, no saves, parameters and buffers untouched) and the saves start
+        at fuse0 .. fuse4.  The caller voids the folded cache after it has moved weights or statistics (invalidate_folded and
+        ops.WEIGHT_EPOCH); this pass voids it itself when a BatchNorm ran in train mode."""
+        if trainable not in self.TRAINABLE:
+            raise ValueError(f"trainable is one of {self.TRAINABLE}, got {trainable!r}")
+        save["trainable"] = trainable
+        if trainable == "decoder":
+            fuses = self._encoders_frozen(rgb, depth)
+        else:
+            stem, s, b = _conv_bn_train(rgb, self.conv1, self.bn1)
+            stem.update(x=rgb, out=ops.bn_apply(stem["raw"], s, b, relu=True))
+            stem_d, s, b = _conv_bn_train(depth, self.conv1_d, self.bn1_d)
+            stem_d.update(x=depth, out=ops.bn_apply(stem_d["raw"], s, b, relu=True))
+            fuses = [ops.add(stem["out"], stem_d["out"])]
+            save["stem"], save["stem_d"], save["blocks"], save["blocks_d"] = stem, stem_d, [], []
+            x, d = ops.pool2d(fuses[0], 3, 2, 1, "max"), ops.pool2d(stem_d["out"], 3, 2, 1, "max")
+            for la, lb in ((self.layer1, self.layer1_d), (self.layer2, self.layer2_d), (self.layer3, self.layer3_d),
+                           (self.layer4, self.layer4_d)):
+                for blk, blk_d in zip(la, lb):
+                    x = _bottleneck_train(blk, x, save["blocks"])
+                    d = _bottleneck_train(blk_d, d, save["blocks_d"])
+                # (a tensor of its own: x and d stay the ReLU masks of the blocks that wrote them)
+                fuses.append(ops.add(x, d))
+                x = fuses[-1]
+        save["fuse0"] = fuses[0]
+        save["agant"], save["deconv"], save["heads"] = [None] * 5, [], []
+        save["agant"][4] = _agant_train(self.agant4, fuses[4])
+        x = save["agant"][4]["out"]
+        outs = []
+        for k, (seq, head) in enumerate(((self.deconv1, self.out5_conv_custom), (self.deconv2, self.out4_conv_custom),
+                                         (self.deconv3, self.out3_conv_custom), (self.deconv4, self.out2_conv_custom))):
+            blocks = []
+            for blk in seq:
+                x = _transblock_train(blk, x, blocks)
+            save["deconv"].append(blocks)
+            save["heads"].append(x)  # the head's input: this stage's output in front of the skip add
+            outs.append(_head_train(head, x))
+            save["agant"][3 - k] = _agant_train((self.agant3, self.agant2, self.agant1, self.agant0)[k], fuses[3 - k])
+            x = ops.add(x, save["agant"][3 - k]["out"])
+        blocks = []
+        for blk in self.final_conv:
+            x = _transblock_train(blk, x, blocks)
+        save["deconv"].append(blocks)
+        save["final"] = x
+        fd = self.final_deconv_custom
+        out = ops.conv_transpose2d(x, ops.weight_oi_transpose(fd.weight), 2, 0, 0, shift=fd.bias)
+        if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
+            self.invalidate_folded()  # (running statistics moved)
+            ops.WEIGHT_EPOCH += 1
+        out5, out4, out3, out2 = outs
+        return out, out2, out3, out4, out5
 
     def forward(self, rgb, depth):
         """rgb (B,3,H,W) normalised, depth (B,1,H,W) normalised -> scores (B,classes,H,W)

@@ -343,6 +343,126 @@ def rgb_encoder_backward(cnn, save, d_feats, G):
     return G
 
 
+# ------------------------------------------------------------------------------------------------
+# RedNet fine-tuning (rednet.RedNet.forward_train)
+# ------------------------------------------------------------------------------------------------
+def _convt_backward(convt, dy, x, G, need_dx=True, residual=None):
+    """Gradients of a bias-free stride-2 transposed conv.  It is the adjoint of a conv with the same (Cin, Cout, k, k) weight:
+    its input gradient is that conv applied to dy, its weight gradient that conv's weight gradient with the roles of x and dy
+    swapped - already in the parameter's layout."""
+    w = convt.weight
+    k, s, p = w.shape[2], convt.stride[0], convt.padding[0]
+    G[w] = ops.conv2d_bwd_weight(x, dy, k, k, s, p)
+    if not need_dx:
+        return None
+    dx = ops.conv2d(dy, w, stride=s, pad=p, residual=residual)
+    if tuple(dx.shape) != tuple(x.shape):
+        raise ops._lib.IvlnError(f"transposed conv backward: input gradient {tuple(dx.shape)} for an input {tuple(x.shape)}")
+    return dx
+
+
+def _any_conv_backward(conv, dy, x, G, need_dx=True, residual=None):
+    fn = _convt_backward if isinstance(conv, torch.nn.ConvTranspose2d) else _conv_backward
+    return fn(conv, dy, x, G, need_dx=need_dx, residual=residual)
+
+
+def _transblock_backward(blk, s, d_out, G):
+    """d(block output) -> d(block input), rednet.TransBasicBlock as rednet._transblock_train saved it - the plain form
+    (conv3x3, conv3x3, identity) and the upsampling one (conv3x3, transposed conv3x3, transposed conv2x2 residual) alike.
+    The tail relu(bn2(c2) + bn_up(up) | identity) masks d_out once, in place (dz)."""
+    d_r2, dz = _bn_backward(blk.bn2, s["l2"], d_out, G, out=s["out"], want_dz=d_out)
+    if blk.upsample is not None:
+        d_ru, _ = _bn_backward(blk.upsample[1], s["up"], dz, G)
+        d_id = _any_conv_backward(blk.upsample[0], d_ru, s["x"], G)
+    else:
+        d_id = dz
+    d_a1 = _any_conv_backward(blk.conv2, d_r2, s["l1"]["out"], G)
+    d_r1, _ = _bn_backward(blk.bn1, s["l1"], d_a1, G, out=s["l1"]["out"])
+    return _conv_backward(blk.conv1, d_r1, s["x"], G, residual=d_id)
+
+
+def _agant_backward(layer, s, dy, G, need_dx=True):
+    """A 1x1 conv -> BatchNorm -> ReLU skip layer; dy is only read."""
+    d_raw, _ = _bn_backward(layer[1], s, dy, G, out=s["out"])
+    return _conv_backward(layer[0], d_raw, s["x"], G, need_dx=need_dx)
+
+
+def _head_backward(conv, d_scores, x, G, residual):
+    """A biased 1x1 score head: fills G, returns residual + its input gradient (a new tensor)."""
+    O, I = conv.weight.shape[:2]
+    d_scores = d_scores.contiguous()
+    G[conv.weight] = ops.conv2d_bwd_weight(d_scores, x, 1, 1)
+    G[conv.bias] = ops.nchw_chansum(d_scores)
+    return ops.conv2d(d_scores, ops.transpose(conv.weight.view(O, I)).view(I, O, 1, 1), residual=residual, weight_is_temp=True)
+
+
+def _dup(t):
+    out = torch.empty_like(t)
+    ops.copy2d(t.view(1, -1), out.view(1, -1), 1, t.numel())
+    return out
+
+
+def rednet_backward(model, save, d_outs, G):
+    """Hand-written backward of rednet.RedNet.forward_train: `save` as that pass left it, d_outs = the gradients of
+    (out, out2, out3, out4, out5).  Walks the saves in reverse - final transposed conv, final_conv, the four decoder stages
+    with their heads, skip adds and `agant` layers, then (trainable "all") the five fusion adds, 2 x 16 bottlenecks, both
+    max-pools and both stems - and fills G for every trainable parameter; the images take no gradient.  Saves are released
+    as they are walked."""
+    trainable = save.pop("trainable")
+    full = trainable == "all"
+    d_out, d_out2, d_out3, d_out4, d_out5 = d_outs
+    fd = model.final_deconv_custom
+    d_out = d_out.contiguous()
+    x = save.pop("final")
+    G[fd.bias] = ops.nchw_chansum(d_out)
+    G[fd.weight] = ops.conv2d_bwd_weight(x, d_out, 2, 2, 2, 0)
+    d = ops.conv2d(d_out, fd.weight, stride=2, pad=0)
+    del x
+    deconv, heads, agant = save.pop("deconv"), save.pop("heads"), save.pop("agant")
+    blocks = deconv.pop()
+    for blk in reversed(model.final_conv):
+        d = _transblock_backward(blk, blocks.pop(), d, G)
+    stages = ((model.deconv4, model.out2_conv_custom, model.agant0, d_out2), (model.deconv3, model.out3_conv_custom, model.agant1, d_out3),
+              (model.deconv2, model.out4_conv_custom, model.agant2, d_out4), (model.deconv1, model.out5_conv_custom, model.agant3, d_out5))
+    d_fuse = [None] * 5
+    for k, (seq, head, ag, d_head) in enumerate(stages):
+        # x = stage output + agant_k(fuse_k): d reaches both addends; the stage output also feeds its head
+        d_fuse[k] = _agant_backward(ag, agant[k], d, G, need_dx=full)
+        agant[k] = None
+        d = _head_backward(head, d_head, heads.pop(), G, residual=d)
+        blocks = deconv.pop()
+        for blk in reversed(seq):
+            d = _transblock_backward(blk, blocks.pop(), d, G)
+    d_fuse[4] = _agant_backward(model.agant4, agant[4], d, G, need_dx=full)
+    del agant, d
+    fuse0 = save.pop("fuse0")
+    if not full:
+        return G
+    # the encoders.  fuse_k = x_k + d_k feeds the RGB branch's next layer and agant_k: d(fuse_k) = both; it is the gradient of
+    # x_k (RGB layer k's output) and, with what the depth branch's next layer sends back, of d_k
+    sv, sv_d = save.pop("blocks"), save.pop("blocks_d")
+    layers = ((model.layer4, model.layer4_d), (model.layer3, model.layer3_d), (model.layer2, model.layer2_d),
+              (model.layer1, model.layer1_d))
+    g_f, g_d = d_fuse[4], None  # d(fuse_k) complete; d(d_k) from the depth branch's layer k + 1
+    for k, (la, lb) in zip((4, 3, 2, 1), layers):
+        g_dep = _dup(g_f) if g_d is None else ops.add(g_f, g_d)  # (a tensor of its own: a block's backward masks its d_out in place)
+        for blk in reversed(la):
+            g_f = _bn_bottleneck_backward(blk, sv.pop(), g_f, G)
+        for blk in reversed(lb):
+            g_dep = _bn_bottleneck_backward(blk, sv_d.pop(), g_dep, G)
+        g_d = g_dep
+        if k > 1:
+            g_f = ops.add(g_f, d_fuse[k - 1])
+    stem, stem_d = save.pop("stem"), save.pop("stem_d")
+    g_f = ops.add(ops.maxpool3s2_bwd(g_f, fuse0), d_fuse[0])  # d(fuse0): the RGB max-pool and agant0
+    g_d = ops.add(ops.maxpool3s2_bwd(g_d, stem_d["out"]), g_f)  # d(depth stem output): its own max-pool and the add
+    d_raw, _ = _bn_backward(model.bn1, stem, g_f, G, out=stem["out"])
+    _conv_backward(model.conv1, d_raw, stem["x"], G, need_dx=False)
+    d_raw, _ = _bn_backward(model.bn1_d, stem_d, g_d, G, out=stem_d["out"])
+    _conv_backward(model.conv1_d, d_raw, stem_d["x"], G, need_dx=False)
+    return G
+
+
 _ZEROS = {}
 
 

@@ -1,0 +1,83 @@
+"""Fine-tunes RedNet on the observation stream tools/build_known_maps.py consumes: drives the project's vector env with the
+expert action of `shortest_path_sensor` and takes one Adam step per batch on (rgb, depth) -> semantic12
+(ivln_ce_amd.rednet_train.RedNetTrainer: five-output pixel cross-entropy, HIP forward and backward), then writes
+{"model_state": state_dict} - the file PredictSemantics.setup reads as data/rednet_mp3d_best_model.pkl.
+
+    python tools/finetune_rednet.py --exp-config <yaml> --steps N --out <file> [--init <ckpt>] [--trainable decoder|all]
+                                    [--lr 2e-4] [--ignore-label L] [KEY VALUE ...]   (trailing config overrides)
+
+Prints one JSON line per 10 steps {step, loss, per_scale} and a last one with the mIoU of the final batch."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--exp-config", required=True)
+    ap.add_argument("--steps", type=int, required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--init", default=None, help='a checkpoint {"model_state": ...} to start from')
+    ap.add_argument("--trainable", choices=("all", "decoder"), default="all")
+    ap.add_argument("--lr", type=float, default=2e-4)
+    ap.add_argument("--ignore-label", type=int, default=None)
+    ap.add_argument("opts", nargs=argparse.REMAINDER)
+    a = ap.parse_args(argv)
+    if a.steps <= 0:
+        ap.error("--steps must be positive")
+    return a
+
+
+def load_model(init, device):
+    from ivln_ce_amd.rednet import PredictSemantics, RedNet
+
+    model = RedNet(PredictSemantics.CFG)
+    if init is not None:
+        state = torch.load(init, map_location="cpu")["model_state"]
+        if next(iter(state)).split(".")[0] == "module":
+            state = {".".join(k.split(".")[1:]): v for k, v in state.items()}
+        model.load_state_dict(state)
+    return model.to(device).train()
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("finetune_rednet: RedNet trains on the GPU (there is no CPU fallback)")
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from build_known_maps import explore  # (the same observation stream)
+
+    from ivln_ce_amd.config import get_config
+    from ivln_ce_amd.envs import construct_envs
+    from ivln_ce_amd.rednet_train import RedNetTrainer
+
+    cfg = get_config(a.exp_config, a.opts or None)
+    device = torch.device("cuda", int(cfg.TORCH_GPU_ID))
+    trainer = RedNetTrainer(load_model(a.init, device), lr=a.lr, trainable=a.trainable, ignore_label=a.ignore_label)
+    envs = construct_envs(cfg, auto_reset_done=True, iterative=False, with_rgb=True)
+    batch = None
+    try:
+        for t, batch in enumerate(explore(envs, a.steps, device)):
+            for key in ("rgb", "depth", "semantic12"):
+                if key not in batch:
+                    raise SystemExit(f"finetune_rednet: the observations carry no `{key}`")
+            loss = trainer.step(batch)
+            if t % 10 == 0 or t + 1 == a.steps:
+                print(json.dumps({"step": t, "loss": loss, "per_scale": trainer.last_per_scale}), flush=True)
+    finally:
+        envs.close()
+    m = trainer.evaluate([batch])
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    trainer.save(a.out)
+    print(json.dumps({"out": a.out, "steps": a.steps, "trainable": a.trainable, "last_batch_miou": m["miou"],
+                      "last_batch_pixel_acc": m["pixel_acc"]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
