@@ -31,6 +31,8 @@ SOURCES = {
     "depth_bwd.hip": [],
     "rgb_bwd.hip": [],
     "seg_loss.hip": [],
+    # (the augmentation's float steps round where they are written, as its float32 restatement in the tests does)
+    "seg_augment.hip": ["-ffp-contract=off"],
     "dtw.cpp": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -57,6 +59,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_build.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_seed.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_train.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_seg_augment.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

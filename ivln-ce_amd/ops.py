@@ -2347,6 +2347,70 @@ def seg_confusion(pred_u8, truth_u8, classes, ignore_label=None, counts=None, ch
     return counts
 
 
+# ---- augmentation and class statistics (include/ivln_seg_augment.h, csrc/seg_augment.hip) ---------------
+def seg_augment(rgb_u8_nhwc, depth, labels_u8, geom, photo, ignore_label=None, out=None):
+    """Scale + crop / pad + flip with one geometry, saturation / value jitter and RedNet's input normalisation as one
+    launch: rgb u8 (B, h, w, 3), depth f32 (B, H, W[, 1]), labels u8 (B, H, W) and one record per image on the HOST -
+    geom int32 (B, 4) {q, oy, ox, flip}, photo f32 (B, 4) {ks, kv, dv, 0} -> rgb_n (B, 3, H, W), depth_n (B, 1, H, W),
+    labels_a u8 (B, H, W).  The C entry point validates the records and passes them as kernel arguments: no
+    synchronisation, no staging buffer.  A bad record raises (IVLN_E_INVALID) before anything is enqueued.  out: the three
+    output tensors to write (contiguous, of those shapes) instead of fresh ones."""
+    if depth.dim() == 4 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if (rgb_u8_nhwc.dtype != torch.uint8 or rgb_u8_nhwc.dim() != 4 or rgb_u8_nhwc.shape[-1] != 3 or depth.dim() != 3
+            or depth.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or labels_u8.shape != depth.shape
+            or rgb_u8_nhwc.shape[0] != depth.shape[0]):
+        raise _lib.IvlnError(f"seg_augment: rgb u8 (B, h, w, 3), depth f32 (B, H, W), labels u8 (B, H, W), got "
+                             f"{tuple(rgb_u8_nhwc.shape)}, {tuple(depth.shape)}, {labels_u8.dtype} {tuple(labels_u8.shape)}")
+    B, h, w, _ = rgb_u8_nhwc.shape
+    _, H, W = depth.shape
+    if (geom.device.type != "cpu" or photo.device.type != "cpu" or geom.dtype != torch.int32 or photo.dtype != torch.float32
+            or tuple(geom.shape) != (B, 4) or tuple(photo.shape) != (B, 4)):
+        raise _lib.IvlnError(f"seg_augment: host records geom int32 ({B}, 4) and photo f32 ({B}, 4)")
+    geom, photo = geom.contiguous(), photo.contiguous()
+    rgb_u8_nhwc, depth, labels_u8 = rgb_u8_nhwc.contiguous(), depth.contiguous(), labels_u8.contiguous()
+    dev = depth.device
+    if out is None:
+        out = (torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               torch.empty((B, 1, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W), dtype=torch.uint8, device=dev))
+    rgb_n, depth_n, labels_a = out
+    for t, shape, dtype in ((rgb_n, (B, 3, H, W), torch.float32), (depth_n, (B, 1, H, W), torch.float32),
+                            (labels_a, (B, H, W), torch.uint8)):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise _lib.IvlnError(f"seg_augment: out = contiguous {shape} {dtype} on {dev}, got {tuple(t.shape)} {t.dtype}")
+    L = _L()
+    L.ivln_seg_augment_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    check(L.ivln_seg_augment_f32(dptr(rgb_u8_nhwc), dptr(depth), dptr(labels_u8), B, h, w, H, W, geom.data_ptr(),
+                                 photo.data_ptr(), -1 if ignore_label is None else int(ignore_label), dptr(rgb_n),
+                                 dptr(depth_n), dptr(labels_a), stream_ptr()), "ivln_seg_augment_f32")
+    return rgb_n, depth_n, labels_a
+
+
+def seg_class_counts(labels_u8, classes, ignore_label=None, pixels=None, present=None, check_labels=True):
+    """u8 labels (B, ...) -> (pixels, present) int64 (classes,), accumulated into the given vectors: pixels[c] += pixels of
+    class c; present[c] += the labelled pixels of every image in which c occurs (median-frequency balancing's two sums)."""
+    if labels_u8.dtype != torch.uint8 or labels_u8.dim() < 2 or labels_u8.numel() == 0:
+        raise _lib.IvlnError(f"seg_class_counts: u8 labels (B, ...), got {labels_u8.dtype} {tuple(labels_u8.shape)}")
+    labels_u8 = labels_u8.contiguous()
+    dev = labels_u8.device
+    B = labels_u8.shape[0]
+    if pixels is None:
+        pixels = torch.zeros(classes, dtype=torch.int64, device=dev)
+    if present is None:
+        present = torch.zeros(classes, dtype=torch.int64, device=dev)
+    if pixels.dtype != torch.int64 or present.dtype != torch.int64 or pixels.numel() != classes or present.numel() != classes:
+        raise _lib.IvlnError(f"seg_class_counts: two int64 vectors of {classes}")
+    _, err = _seg_ws(dev)
+    L = _L()
+    L.ivln_seg_class_counts_u8.argtypes = [vp, i32, i64, i32, i32, vp, vp, vp, vp]
+    check(L.ivln_seg_class_counts_u8(dptr(labels_u8), B, labels_u8.numel() // B, classes,
+                                     -1 if ignore_label is None else int(ignore_label), dptr(pixels), dptr(present), dptr(err),
+                                     stream_ptr()), "ivln_seg_class_counts_u8")
+    if check_labels:
+        seg_check(dev, "seg_class_counts")
+    return pixels, present
+
+
 # ---- GEMM-shaped gradients ----------------------------------------------------------------------------
 def linear_bwd_input(dy, w, out=None, accumulate=False, splits=None, info=None):
     """dX[r][i] = sum_o dY[r][o] W[o][i]  (dy, out may be row-strided)."""
