@@ -60,6 +60,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_map_seed.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_train.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_augment.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_tour_state.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

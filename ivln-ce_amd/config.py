@@ -299,6 +299,10 @@ def _experiment_defaults() -> Config:
     _C.MODEL.STATE_ENCODER = CN()
     _C.MODEL.STATE_ENCODER.hidden_size = 512
     _C.MODEL.STATE_ENCODER.rnn_type = "GRU"
+    # (not a key of the reference) LatentCMAPolicy takes rnn_type LSTM only with this switch on: its tour-memory variant
+    # then follows a definition of this project - the reference raises there ("Latent-CMA with LSTM state
+    # encoders") - and a config that merely sets rnn_type keeps the ValueError it always got
+    _C.MODEL.STATE_ENCODER.latent_lstm = False
     _C.MODEL.PROGRESS_MONITOR = CN()
     _C.MODEL.PROGRESS_MONITOR.use = False
     _C.MODEL.PROGRESS_MONITOR.alpha = 1.0

@@ -11,7 +11,9 @@
 //    most of its 13 us in 48 full-wave reductions per block).  H workgroups of 256 threads cover the chip twice at H = 512.
 // 2. A sequence as T such launches enqueued back to back from ONE C call (the per-timestep Python -> ctypes round trip,
 //    ~15 us, was longer than the 6.5 us kernel), BPTT likewise as one launch per timestep: the carry of step t (a skinny
-//    matvec against W_hh^T) fused with the element part of step t-1 on the same hidden unit.
+//    matvec against W_hh^T) fused with the element part of step t-1 on the same hidden unit.  Latent-CMA's
+//    `tour_memory_variant` feeds its first encoder a memory pooled with that encoder's previous output, so no W_ih x can
+//    be precomputed for that segment: k_rnn_step_tour is the step with the memory update inside it, enqueued the same way.
 // 3. The GRU sequence and its BPTT as ONE persistent launch each, inside an envelope (H = 512, N <= 64 / 16); the LSTM has
 //    no persistent form.  Design:
 //   * 64 workgroups x 256 threads; workgroup b owns hidden units [8 b, 8 b + 8).  A 32-lane group owns one unit and keeps
@@ -46,6 +48,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/ivln_hip.h"
+#include "../../include/ivln_tour_state.h"
 #include "residency.h"
 #include "rnn_cell.h"
 
@@ -146,6 +149,147 @@ Saves saves_at(const Saves& all, int64_t off) {
     Saves sv;
     for (int i = 0; i < 5; ++i) sv.p[i] = all.p[0] && all.p[i] ? all.p[i] + off : nullptr;
     return sv;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The masked step with Latent-CMA's tour-long memory inside it (include/ivln_tour_state.h): k_rnn_step's work split
+// (workgroup j = hidden unit j, LPR lanes per state row, one shuffle reduction per (row, unit)) for an encoder whose
+// input ends in a memory segment that depends on its own previous output,
+//   m = tour_mask ? (pool ? max(mem_prev, h_in) : mem_prev) : 0        (pool: every step but the first of a call)
+//   gi = gi_base + W_ih[:, I0:I0+H] . m                                 (gi_base = W_ih[:, :I0] x + b_ih, precomputed)
+// Every workgroup recomputes all H values of m from the rows of the step before (h_in is both the recurrent state and
+// what the memory is pooled with: one load serves both); it writes m[j], never reads this step's m_out.  mem_state, when
+// given, takes max(m, h_t) - the slot the next call starts from.  c_in / c_out as in k_rnn_step.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float tour_m(float mem, float h, bool keep, bool pool) {
+    return keep ? (pool ? fmaxf(mem, h) : mem) : 0.f;
+}
+
+// gate_dots for this step: unit j's NG rows of W_hh against h * mk AND of the memory segment of W_ih (w_mem = W_ih + I0,
+// row stride ldw) against m, in ONE pass over H with the same lane-strided split; the lanes' partial sums are returned.
+template <int NG, int LPR, bool VEC>
+__device__ __forceinline__ void tour_gate_dots(const float* __restrict__ w_hh, const float* __restrict__ w_mem, int64_t ldw,
+                                               int j, int H, const float* __restrict__ h, float mk,
+                                               const float* __restrict__ mem, bool keep, bool pool, int l, float (&am)[NG],
+                                               float (&ah)[NG]) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) am[g] = ah[g] = 0.f;
+    if constexpr (VEC) {
+        for (int k = l * 4; k < H; k += LPR * 4) {
+            float4 hv = *reinterpret_cast<const float4*>(h + k);
+            float4 mv = *reinterpret_cast<const float4*>(mem + k);
+            mv.x = tour_m(mv.x, hv.x, keep, pool), mv.y = tour_m(mv.y, hv.y, keep, pool);
+            mv.z = tour_m(mv.z, hv.z, keep, pool), mv.w = tour_m(mv.w, hv.w, keep, pool);
+            hv.x *= mk, hv.y *= mk, hv.z *= mk, hv.w *= mk;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ah[g] = fma4(*reinterpret_cast<const float4*>(w_hh + ((int64_t)g * H + j) * H + k), hv, ah[g]);
+                am[g] = fma4(*reinterpret_cast<const float4*>(w_mem + ((int64_t)g * H + j) * ldw + k), mv, am[g]);
+            }
+        }
+    } else {
+        for (int k = l; k < H; k += LPR) {
+            const float hk = h[k];
+            const float mv = tour_m(mem[k], hk, keep, pool), hv = hk * mk;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ah[g] = fmaf(w_hh[((int64_t)g * H + j) * H + k], hv, ah[g]);
+                am[g] = fmaf(w_mem[((int64_t)g * H + j) * ldw + k], mv, am[g]);
+            }
+        }
+    }
+}
+
+template <class Cell, int LPR, bool VEC>
+__global__ __launch_bounds__(256) void k_rnn_step_tour(
+    const float* __restrict__ gi_base, const float* __restrict__ h_in, int64_t ldh, const float* c_in, int64_t ldc,
+    const float* __restrict__ mem_prev, int64_t ldm, int pool, const uint8_t* __restrict__ ep_mask,
+    const uint8_t* __restrict__ tour_mask, const float* __restrict__ w_mem, int64_t ldw, const float* __restrict__ w_hh,
+    const float* __restrict__ b_hh, float* __restrict__ h_out, int64_t ldo, float* __restrict__ m_out, int64_t ldmo,
+    float* __restrict__ h_out2, int64_t ldo2, float* c_out, int64_t ldco, float* __restrict__ mem_state, int64_t ldms,
+    int rows, int H, float* __restrict__ save0, float* __restrict__ save1, float* __restrict__ save2,
+    float* __restrict__ save3, float* __restrict__ save4) {
+    constexpr int NG = Cell::NG;
+    constexpr int RPB = 256 / LPR;  // rows per pass
+    const int j = blockIdx.x;
+    const int l = threadIdx.x % LPR, rr = threadIdx.x / LPR;
+    for (int r0 = 0; r0 < rows; r0 += RPB) {
+        const int row = r0 + rr;
+        const bool row_ok = row < rows;
+        const int rowc = row_ok ? row : 0;
+        const float mk = ep_mask[rowc] ? 1.f : 0.f;
+        const bool keep = tour_mask[rowc] != 0;
+        const float* hr = h_in + (int64_t)rowc * ldh;
+        const float* mr = mem_prev + (int64_t)rowc * ldm;
+        float am[NG], ah[NG];
+        tour_gate_dots<NG, LPR, VEC>(w_hh, w_mem, ldw, j, H, hr, mk, mr, keep, pool != 0, l, am, ah);
+        lpr_sum_gates<LPR>(am, true, ah);
+        if (l == 0 && row_ok) {
+            float gi[NG], gh[NG], sv[5];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                gi[g] = gi_base[(int64_t)row * NG * H + g * H + j] + am[g];
+                gh[g] = ah[g] + (b_hh ? b_hh[g * H + j] : 0.f);
+            }
+            const float hj = hr[j];
+            const float mj = tour_m(mr[j], hj, keep, pool != 0);
+            const float prev = (Cell::HAS_C ? c_in[(int64_t)row * ldc + j] : hj) * mk;
+            const float hn = Cell::fwd(gi, gh, prev, sv);
+            h_out[(int64_t)row * ldo + j] = hn;
+            m_out[(int64_t)row * ldmo + j] = mj;
+            if (h_out2) h_out2[(int64_t)row * ldo2 + j] = hn;
+            if (mem_state) mem_state[(int64_t)row * ldms + j] = fmaxf(mj, hn);
+            if constexpr (Cell::HAS_C) c_out[(int64_t)row * ldco + j] = sv[4];
+            if (save0) {
+                const int64_t e = (int64_t)row * H + j;
+                save0[e] = sv[0], save1[e] = sv[1], save2[e] = sv[2], save3[e] = sv[3];
+                if constexpr (Cell::NSAVE == 5) save4[e] = sv[4];
+            }
+        }
+    }
+}
+
+// the bytes from the first to the last element of a (rows, H) view with row stride ld
+struct Span {
+    uintptr_t lo, hi;
+};
+inline Span span_of(const void* p, int64_t rows, int64_t ld, int64_t H) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return {lo, p ? lo + (uintptr_t)(((rows - 1) * ld + H) * (int64_t)sizeof(float)) : lo};
+}
+inline bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// A whole sequence of such steps, enqueued back to back (ivln_lstm_seq_fwd_f32's shape).  The load form is chosen ONCE
+// for the sequence, so every step runs the same arithmetic.  The caller has validated sizes and overlaps.
+template <class Cell>
+void launch_tour_seq(const float* gi_base, const float* w_ih, int I0, const float* w_hh, const float* b_hh,
+                     const float* h0, int64_t ld_h0, const float* c0, int64_t ld_c0, const float* mem0, int64_t ld_m0,
+                     const uint8_t* ep_masks, const uint8_t* tour_masks, float* out, int64_t ldo, float* mem_in,
+                     int64_t ld_mi, float* h_state_out, int64_t ld_hs, float* c_state_out, int64_t ld_cs,
+                     float* mem_state_out, int64_t ld_ms, int T, int N, int H, const Saves& all, hipStream_t s) {
+    const float* w_mem = w_ih + I0;
+    const int64_t ldw = (int64_t)I0 + H;
+    const bool vec = al16(h0) && al16(mem0) && al16(out) && al16(mem_in) && al16(w_hh) && al16(w_mem) &&
+                     !((ld_h0 | ld_m0 | ldo | ld_mi | ldw) & 3);
+    for (int t = 0; t < T; ++t) {
+        const int64_t r0 = (int64_t)t * N;
+        const bool last = t == T - 1;
+        const float* h_in = t == 0 ? h0 : out + (r0 - N) * ldo;
+        const float* m_prev = t == 0 ? mem0 : mem_in + (r0 - N) * ld_mi;
+        const Saves sv = saves_at(all, r0 * H);
+#define IVLN_TOUR_STEP(LPR, VEC)                                                                                          \
+    hipLaunchKernelGGL((k_rnn_step_tour<Cell, LPR, VEC>), dim3(H), dim3(256), 0, s, gi_base + r0 * Cell::NG * H, h_in,    \
+                       t == 0 ? ld_h0 : ldo, t == 0 ? c0 : c_state_out, t == 0 ? ld_c0 : ld_cs, m_prev,                   \
+                       t == 0 ? ld_m0 : ld_mi, t == 0 ? 0 : 1, ep_masks + r0, tour_masks + r0, w_mem, ldw, w_hh, b_hh,    \
+                       out + r0 * ldo, ldo, mem_in + r0 * ld_mi, ld_mi, last ? h_state_out : nullptr, ld_hs, c_state_out,  \
+                       ld_cs, last ? mem_state_out : nullptr, ld_ms, N, H, sv.p[0], sv.p[1], sv.p[2], sv.p[3], sv.p[4])
+        if (vec) {
+            if (N <= 4) IVLN_TOUR_STEP(64, true); else IVLN_TOUR_STEP(32, true);
+        } else {
+            if (N <= 4) IVLN_TOUR_STEP(64, false); else IVLN_TOUR_STEP(32, false);
+        }
+#undef IVLN_TOUR_STEP
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -792,6 +936,37 @@ int ivln_lstm_seq_fwd_f32(const float* gi, const float* h0, int64_t ld_h0, const
                               w_hh, nullptr, b_hh, out + r0 * ldo, ldo, t == T - 1 ? h_state_out : nullptr, ld_hs,
                               c_state_out, ld_cs, N, H, saves_at(all, r0 * H), (hipStream_t)stream);
     }
+    return LAUNCH_OK();
+}
+
+int ivln_lstm_seq_tour_fwd_f32(const float* gi_base, const float* w_ih, int I0, const float* w_hh, const float* b_hh,
+                               const float* h0, int64_t ld_h0, const float* c0, int64_t ld_c0, const float* mem0,
+                               int64_t ld_m0, const uint8_t* ep_masks, const uint8_t* tour_masks, float* out, int64_t ldo,
+                               float* mem_in, int64_t ld_mi, float* h_state_out, int64_t ld_hs, float* c_state_out,
+                               int64_t ld_cs, float* mem_state_out, int64_t ld_ms, int T, int N, int H, float* save_i,
+                               float* save_f, float* save_g, float* save_o, float* save_c, void* stream) {
+    if (!gi_base || !w_ih || !w_hh || !h0 || !c0 || !mem0 || !ep_masks || !tour_masks || !out || !mem_in || !c_state_out ||
+        !mem_state_out || T <= 0 || N <= 0 || H <= 0 || (H & 3) || I0 <= 0)
+        return IVLN_E_INVALID;
+    if (save_i && (!save_f || !save_g || !save_o || !save_c)) return IVLN_E_INVALID;
+    if (ld_h0 < H || ld_c0 < H || ld_m0 < H || ldo < H || ld_mi < H || ld_cs < H || ld_ms < H || (h_state_out && ld_hs < H))
+        return IVLN_E_INVALID;
+    // every workgroup reads whole rows of h0 / mem0 (and element (n, j) of c0) while others write: no output may overlap them
+    const int64_t TN = (int64_t)T * N;
+    const Span outs[] = {span_of(out, TN, ldo, H),          span_of(mem_in, TN, ld_mi, H),
+                         span_of(h_state_out, N, ld_hs, H), span_of(c_state_out, N, ld_cs, H),
+                         span_of(mem_state_out, N, ld_ms, H), span_of(save_i, TN, H, H),
+                         span_of(save_f, TN, H, H),         span_of(save_g, TN, H, H),
+                         span_of(save_o, TN, H, H),         span_of(save_c, TN, H, H)};
+    const Span ins[] = {span_of(h0, N, ld_h0, H), span_of(mem0, N, ld_m0, H), span_of(c0, N, ld_c0, H)};
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 10; ++b) {
+            if (a == 2 && b == 3 && c0 == c_state_out && ld_c0 == ld_cs) continue;  // the cell state advanced in place
+            if (overlap(ins[a], outs[b])) return IVLN_E_INVALID;
+        }
+    launch_tour_seq<LstmCell>(gi_base, w_ih, I0, w_hh, b_hh, h0, ld_h0, c0, ld_c0, mem0, ld_m0, ep_masks, tour_masks, out,
+                              ldo, mem_in, ld_mi, h_state_out, ld_hs, c_state_out, ld_cs, mem_state_out, ld_ms, T, N, H,
+                              {{save_i, save_f, save_g, save_o, save_c}}, (hipStream_t)stream);
     return LAUNCH_OK();
 }
 

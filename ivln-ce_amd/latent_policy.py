@@ -7,6 +7,9 @@ sequence mode and the tour-memory variant the reference unrolls) run on the HIP 
 RGB ResNet-50 is the BN-folded bottleneck stack already used by RedNet (MFMA convs with fused scale/shift/
 residual/ReLU epilogues), the head reuses the MapCMA kernels (instruction bi-LSTM, DD-PPO depth ResNet,
 GRU steps and BPTT, attention forward/backward); `backward_hip` is the hand-written backward.
+`MODEL.STATE_ENCODER.rnn_type: LSTM` with `MODEL.STATE_ENCODER.latent_lstm: True` gives both state encoders as LSTMs
+(state [h1, c1, h2, c2 (, memory)]); with the tour-memory variant the first one runs through the step kernel that updates
+the memory itself (include/ivln_tour_state.h).
 """
 from typing import Tuple
 
@@ -17,8 +20,8 @@ from torch import Tensor
 
 from . import ops
 from .aux_losses import AuxLosses
-from .encoders import InstructionEncoder, VlnResnetDepthEncoder, build_rnn_state_encoder
-from .policy import ILPolicy, Net
+from .encoders import InstructionEncoder, LSTMStateEncoder, VlnResnetDepthEncoder, build_rnn_state_encoder
+from .policy import ILPolicy, MapCMANet, Net
 from .rednet import Bottleneck, _Folded, _bottleneck_train, _conv_bn_train  # noqa: F401  (the train-mode layer helpers live beside Bottleneck)
 from .registry import baseline_registry
 
@@ -145,15 +148,18 @@ class _ResNet50Body(nn.Sequential):
 
 class LatentCMANet(Net):
     """latent_cma_policy.py:195-497 (inference): instruction bi-LSTM, DD-PPO depth ResNet, torchvision RGB
-    ResNet-50, two GRU state encoders, three attentions, optional cross-episode tour memory."""
+    ResNet-50, two GRU or LSTM state encoders (MODEL.STATE_ENCODER.rnn_type), three attentions, optional cross-episode
+    tour memory."""
 
     def __init__(self, observation_space, model_config, num_actions):
         super().__init__()
         self.model_config = model_config
-        if str(model_config.STATE_ENCODER.rnn_type).lower() != "gru":
-            # forward_hip / backward_hip below are GRU arithmetic; the LSTM state encoder is MapCMA-only so far
-            raise ValueError("LatentCMANet supports MODEL.STATE_ENCODER.rnn_type GRU only, got "
-                             f"{model_config.STATE_ENCODER.rnn_type!r}")
+        if (str(model_config.STATE_ENCODER.rnn_type).lower() != "gru"
+                and not model_config.STATE_ENCODER.get("latent_lstm", False)):
+            # LSTM state encoders are opt-in here: the tour-memory variant with them is this project's definition, not the
+            # reference's (which raises), and a config that only sets rnn_type is refused as it always was
+            raise ValueError("LatentCMANet takes MODEL.STATE_ENCODER.rnn_type other than GRU only with "
+                             f"MODEL.STATE_ENCODER.latent_lstm True, got {model_config.STATE_ENCODER.rnn_type!r}")
         model_config.defrost()
         model_config.INSTRUCTION_ENCODER.final_state_only = False
         model_config.freeze()
@@ -226,6 +232,15 @@ class LatentCMANet(Net):
     def num_recurrent_layers(self):
         return (self.state_encoder.num_recurrent_layers + self.second_state_encoder.num_recurrent_layers
                 + int(self.model_config.tour_memory_variant))
+
+    def _state_slots(self, states):
+        """The batch-first (N, L, H) state as its users take it (latent_cma_policy.py:392-399,427-431,470-477 slice by each
+        encoder's num_recurrent_layers): first encoder, second encoder - (N, H) for a GRU, (N, 2, H) [h | c] for an LSTM -
+        and the tour-long memory slot behind them (None without `tour_memory_variant`)."""
+        s1, s2 = self.state_encoder.num_recurrent_layers, self.second_state_encoder.num_recurrent_layers
+        slot = MapCMANet._state_slot
+        mem = states[:, s1 + s2] if self.model_config.tour_memory_variant else None
+        return slot(states, 0, s1), slot(states, s1, s2), mem
 
     def forward(self, observations, rnn_states, prev_actions, action_masks, episode_masks=None, tour_masks=None):
         """Same signature/return as latent_cma_policy.py:375-497.  rows == envs: one step; rows == T*envs: a
@@ -327,7 +342,28 @@ class LatentCMANet(Net):
         s_g1 = {} if save is not None else None
         s_g2 = {} if save is not None else None
         mem_in = None
-        if variant:
+        if isinstance(self.state_encoder, LSTMStateEncoder):
+            # STATE_ENCODER.rnn_type LSTM: state [h1, c1, h2, c2 (, memory)]
+            in1, _, mem0 = self._state_slots(rnn_states)
+            out1, _, mem_out = self._state_slots(rnn_out)
+            if variant:
+                # The memory is pooled with h, the first encoder's OUTPUT ("Latent-CMA with LSTM state encoders": the
+                # reference has no LSTM form of this).  One call enqueues the T steps, each with the memory update in
+                # it (include/ivln_tour_state.h); the kernel leaves the memory half of state_in behind for the BPTT's
+                # dW_ih and `memory_at_end`.  The memory carries no gradient: _lstm_backward sees a constant input.
+                rnn = self.state_encoder.rnn
+                tour_u8 = tour_masks.reshape(-1).to(torch.uint8).contiguous()
+                mem_in = state_in[:, base:]
+                gi = ops.linear_gemm(state_in[:, :base], rnn.weight_ih_l0, rnn.bias_ih_l0, w_prefix=True)
+                saves = None
+                if save is not None:
+                    saves = tuple(torch.empty((rows, H), dtype=torch.float32, device=dev) for _ in range(5))
+                    s_g1.update(saves=saves, T=T, N=N, x=state_in, h0=in1[:, 0], c0=in1[:, 1], masks=ep_u8, out=state)
+                ops.lstm_seq_tour(gi, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_hh_l0, in1[:, 0], in1[:, 1], mem0,
+                                  ep_u8, tour_u8, state, mem_in, out1[:, 0], out1[:, 1], mem_out, T, N, saves)
+            else:
+                self.state_encoder(state_in, in1, ep_u8, state, out1, s_g1)
+        elif variant:
             # the tour-long slot: cleared where a tour starts, fed to the first GRU, then max-pooled with that
             # GRU's new state (latent_cma_policy.py:395-399,422-425,433-439).  It carries no gradient in the
             # reference (updated under no_grad from a detached clone), so it is a constant input here too; the
@@ -379,7 +415,8 @@ class LatentCMANet(Net):
         sc = self.second_state_compress[0]
         c2 = ops.linear(x2, sc.weight, sc.bias, relu=True)
         g2_out = torch.empty((rows, H), dtype=torch.float32, device=dev)
-        self.second_state_encoder(c2, rnn_states[:, 1], ep_u8, g2_out, rnn_out[:, 1], s_g2)
+        # (slot 1 for GRU encoders, slots 2:4 for LSTM ones)
+        self.second_state_encoder(c2, self._state_slots(rnn_states)[1], ep_u8, g2_out, self._state_slots(rnn_out)[1], s_g2)
         feats, cat = g2_out, None
         if mc.memory_at_end:
             ol = self.out_layer[0]
@@ -399,7 +436,7 @@ class LatentCMANet(Net):
         `forward_hip` (the RGB and the depth ResNet are traversed only when they train; their learned spatial embeddings
         always are)."""
         from . import train as _train
-        from .train import _conv1d_backward, _gru_backward, instruction_backward
+        from .train import _conv1d_backward, _state_encoder_backward, instruction_backward
 
         G = {}
         mc = self.model_config
@@ -420,7 +457,7 @@ class LatentCMANet(Net):
             G[ol.bias] = ops.colsum(d_pre)
             d_feats = ops.linear_bwd_input(d_pre, ol.weight)[:, :H]
 
-        d_c2 = _gru_backward(self.second_state_encoder, S["g2"], d_feats, G)
+        d_c2 = _state_encoder_backward(self.second_state_encoder, S["g2"], d_feats, G)
         d_pre = ops.relu_bwd(d_c2, S["c2"])
         sc = self.second_state_compress[0]
         G[sc.weight] = ops.linear_bwd_weight(d_pre, x2)
@@ -462,7 +499,7 @@ class LatentCMANet(Net):
         d_state = dx2[:, :H]
         ops.linear_bwd_input(dq1, self.state_q.weight, out=d_state, accumulate=True)
 
-        d_state_in = _gru_backward(self.state_encoder, S["g1"], d_state, G)  # (rows, 288 [+ 512 memory: unused])
+        d_state_in = _state_encoder_backward(self.state_encoder, S["g1"], d_state, G)  # (rows, 288 [+ 512 memory: unused])
         emb = self.prev_action_embedding
         G[emb.weight] = ops.prev_action_embed_bwd(S["prev_actions"], S["act_masks"],
                                                   d_state_in[:, r_out + d_out:r_out + d_out + E], dx2[:, o_prev:],

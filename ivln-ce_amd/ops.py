@@ -151,6 +151,9 @@ def _L():
                                             vp, vp, vp, vp, vp]
         L.ivln_lstm_seq_bwd_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32,
                                             vp, vp, vp, i64, vp, i64, vp]
+        # include/ivln_tour_state.h
+        L.ivln_lstm_seq_tour_fwd_f32.argtypes = ([vp, vp, i32, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp]
+                                                 + [vp, i64] * 5 + [i32, i32, i32] + [vp] * 6)
         _sigs_done = True
     return L
 
@@ -786,17 +789,20 @@ def conv_transpose2d_s2(x, classes, scale=None, shift=None, residual=None, relu=
     return out
 
 
-def linear_gemm(x, w, bias=None, relu=False, out=None):
-    """y[r][o] = act(x[r] . w[o] + b[o]) through the MFMA GEMM (many rows)."""
+def linear_gemm(x, w, bias=None, relu=False, out=None, w_prefix=False):
+    """y[r][o] = act(x[r] . w[o] + b[o]) through the MFMA GEMM (many rows).  `w_prefix`: w has MORE columns than x and
+    only its first x.shape[1] take part (the rows of w keep their stride)."""
     rows, K = x.shape
     O = w.shape[0]
+    if w_prefix and (w.dim() != 2 or w.shape[1] < K):
+        raise _lib.IvlnError(f"linear_gemm: x has {K} columns, w {tuple(w.shape)}")
     if out is None:
         out = torch.empty((rows, O), dtype=torch.float32, device=x.device)
     d = GemmDesc()
     d.A, d.B, d.D = dptr(w), _p(x), _p(out)
     d.M, d.N, d.K = O, rows, K
     d.amode, d.bmode, d.dmode = A_MK, B_NK, D_DENSE
-    d.lda, d.ldb = K, x.stride(0)
+    d.lda, d.ldb = (w.shape[1] if w_prefix else K), x.stride(0)
     d.sDm, d.sDn = 1, out.stride(0)
     d.HoWo = 1
     _epilogue(d, None, bias, None, relu)
@@ -1620,6 +1626,44 @@ def lstm_seq(gi, h0, c0, masks_u8, w_hh, b_hh, out, h_state_out, c_state_out, T,
                                   dptr(b_hh), _p(out), out.stride(0), _p(h_state_out), _ld(h_state_out), _p(c_state_out),
                                   c_state_out.stride(0), T, N, H, *[_p(t) for t in s], stream_ptr()),
           "ivln_lstm_seq_fwd_f32")
+
+
+def lstm_seq_tour(gi_base, w_ih, w_hh, b_hh, h0, c0, mem0, ep_masks_u8, tour_masks_u8, out, mem_in, h_state_out,
+                  c_state_out, mem_state_out, T, N, saves=None):
+    """The first LSTM state encoder of Latent-CMA's `tour_memory_variant` over T timesteps of N rows in one C-ABI call
+    (include/ivln_tour_state.h): T dependent launches of the masked step with the tour-memory update inside it.
+    gi_base (T*N,4H) contiguous = W_ih[:, :I0] x + b_ih; w_ih (4H, I0+H) whole; h0 / c0 / mem0 (N,H) row-strided slots of
+    the incoming state; out / mem_in (T*N,H) row-strided; h_state_out (optional) / c_state_out / mem_state_out (N,H)
+    row-strided slots of the outgoing state; saves: (i, f, g, o, c) (T*N,H) contiguous each, or None.  T = 1: the rollout
+    step."""
+    H = w_hh.shape[1]
+    I0 = w_ih.shape[1] - H
+    rows = T * N
+    if w_ih.shape[0] != 4 * H or w_hh.shape[0] != 4 * H or I0 <= 0:
+        raise _lib.IvlnError(f"lstm_seq_tour: w_ih {tuple(w_ih.shape)} / w_hh {tuple(w_hh.shape)} are not (4H, I0+H) / (4H, H)")
+    if tuple(gi_base.shape) != (rows, 4 * H):
+        raise _lib.IvlnError(f"lstm_seq_tour: gi_base {tuple(gi_base.shape)} is not ({rows}, {4 * H})")
+    for name, t, r in (("h0", h0, N), ("c0", c0, N), ("mem0", mem0, N), ("out", out, rows), ("mem_in", mem_in, rows),
+                       ("h_state_out", h_state_out, N), ("c_state_out", c_state_out, N),
+                       ("mem_state_out", mem_state_out, N)):
+        if t is None and name == "h_state_out":
+            continue
+        if tuple(t.shape) != (r, H) or t.stride(1) != 1 or t.dtype != torch.float32:
+            raise _lib.IvlnError(f"lstm_seq_tour: {name} must be a float32 ({r}, {H}) view with unit column stride")
+    for name, m in (("ep_masks", ep_masks_u8), ("tour_masks", tour_masks_u8)):
+        if m.dtype != torch.uint8 or m.numel() != rows:
+            raise _lib.IvlnError(f"lstm_seq_tour: {name} must be {rows} uint8 values")
+    s = saves or (None,) * 5
+    if saves is not None and any(tuple(t.shape) != (rows, H) for t in saves):
+        raise _lib.IvlnError(f"lstm_seq_tour: every save must be ({rows}, {H})")
+    L = _L()
+    check(L.ivln_lstm_seq_tour_fwd_f32(dptr(gi_base), dptr(w_ih), I0, dptr(w_hh), dptr(b_hh) if b_hh is not None else None,
+                                       _p(h0), h0.stride(0), _p(c0), c0.stride(0), _p(mem0), mem0.stride(0),
+                                       dptr(ep_masks_u8), dptr(tour_masks_u8), _p(out), out.stride(0), _p(mem_in),
+                                       mem_in.stride(0), _p(h_state_out), _ld(h_state_out), _p(c_state_out),
+                                       c_state_out.stride(0), _p(mem_state_out), mem_state_out.stride(0), T, N, H,
+                                       *[dptr(t) if t is not None else None for t in s], stream_ptr()),
+          "ivln_lstm_seq_tour_fwd_f32")
 
 
 def lstm_seq_bwd(d_out, saves, out, h0, c0, masks_u8, whh_t, T, N, dgi, hp, dh0, dc0):
