@@ -36,6 +36,10 @@ from .utils import (ONCE_KEYS, add_batched_data_to_observations, batch_obs, batc
                     dedupe_instructions, expand_once_records,
                     extract_instruction_tokens, trim_instruction_padding)
 
+# observation keys that only served to build the maps: dropped from what the collection loops store once a step's maps are
+# in the observation (iterative_collection_dagger_trainer.py:28-58)
+MAP_SOURCE_KEYS = ("semantic", "semantic12", "world_robot_pose", "world_robot_orientation", "env_name")
+
 
 # ------------------------------------------------------------------------------------------------
 # optimizer: fused Adam over a flat bucket (params and grads become views of two flat tensors)
@@ -533,19 +537,35 @@ class BaseVLNCETrainer:
                             weights, self.config.MODEL.STATE_ENCODER.hidden_size, step_grad, loss_accumulation_scalar,
                             self.world)
 
+    def _initial_state(self, config, n, iterative=False):
+        """The state rows a rollout of `n` envs starts with: (rnn_states, prev_actions, not-done masks...) - one mask,
+        or the iterative protocol's agent-episode / sim-episode / tour masks (0) and action mask (1)."""
+        rnn_states = torch.zeros(n, self.policy.net.num_recurrent_layers, config.MODEL.STATE_ENCODER.hidden_size,
+                                 device=self.device)
+        prev_actions = torch.zeros(n, 1, device=self.device, dtype=torch.long)
+        masks = [torch.zeros(n, 1, dtype=torch.uint8, device=self.device) for _ in range(3 if iterative else 1)]
+        if iterative:
+            masks.append(torch.ones(n, 1, dtype=torch.uint8, device=self.device))
+        return (rnn_states, prev_actions, *masks)
+
+    @staticmethod
+    def _compact_rows(envs_to_pause, envs, rows, batch):
+        """Pause the envs (last first) and drop their rows from the per-env tensors `rows` and from every entry of
+        `batch` (in place).  -> (the kept row indices, the compacted `rows`)"""
+        state_index = list(range(envs.num_envs))
+        for idx in reversed(envs_to_pause):
+            state_index.pop(idx)
+            envs.pause_at(idx)
+        for k, v in batch.items():
+            batch[k] = v[state_index] if torch.is_tensor(v) else [v[i] for i in state_index]
+        return state_index, [r[state_index] for r in rows]
+
     @staticmethod
     def _pause_envs(envs_to_pause, envs, recurrent_hidden_states, not_done_masks, prev_actions, batch, rgb_frames=None):
         """base_il_trainer.py:221-256."""
         if len(envs_to_pause) > 0:
-            state_index = list(range(envs.num_envs))
-            for idx in reversed(envs_to_pause):
-                state_index.pop(idx)
-                envs.pause_at(idx)
-            recurrent_hidden_states = recurrent_hidden_states[state_index]
-            not_done_masks = not_done_masks[state_index]
-            prev_actions = prev_actions[state_index]
-            for k, v in batch.items():
-                batch[k] = v[state_index] if torch.is_tensor(v) else [v[i] for i in state_index]
+            _, (recurrent_hidden_states, not_done_masks, prev_actions) = BaseVLNCETrainer._compact_rows(
+                envs_to_pause, envs, (recurrent_hidden_states, not_done_masks, prev_actions), batch)
         return envs, recurrent_hidden_states, not_done_masks, prev_actions, batch, rgb_frames
 
     def _persistent_guard(self, runner, redo_eager):
@@ -725,48 +745,20 @@ class BaseVLNCETrainer:
                 return json.load(open(fname))
         envs = construct_envs(config, None, auto_reset_done=False, rank=self.rank, world=self.world, iterative=False)
         self._load_eval_policy(config, envs, checkpoint_path)
-        n = envs.num_envs
-        rnn_states = torch.zeros(n, self.policy.net.num_recurrent_layers, config.MODEL.STATE_ENCODER.hidden_size,
-                                 device=self.device)
-        prev_actions = torch.zeros(n, 1, device=self.device, dtype=torch.long)
-        not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
+        rnn_states, prev_actions, not_done_masks = self._initial_state(config, envs.num_envs)
         use_graph = self._graph_eligible()
+        stepper = _PolicyStepper(self, False, use_graph, deterministic=not config.EVAL.SAMPLE)
         observations = envs.reset()
         observations, batch = self._batch(observations, not_done_masks, transform=not use_graph)
         stats_episodes = {}
         episodes_to_eval = sum(envs.number_of_episodes)
         if config.EVAL.EPISODE_COUNT > -1:
             episodes_to_eval = min(config.EVAL.EPISODE_COUNT, episodes_to_eval)
-        runner, captured, eager_once = None, False, False
         t0 = time.time()
         while envs.num_envs > 0 and len(stats_episodes) < episodes_to_eval:
             current_episodes = envs.current_episodes()
-            if use_graph and not eager_once:  # mapper + policy.act replayed as captured graphs; the state lives in
-                if runner is None:            # the runner's buffers
-                    runner = self._make_runner(batch, rnn_states, prev_actions, first=not captured)
-                    captured = True
-                actions = runner.step(batch)
-                rnn_states, prev_actions = runner.rnn_states, actions
-                if depth_net.armed():  # (a persistent launch is part of the step: its time-out flag is read after the sync)
-                    torch.cuda.current_stream().synchronize()
-                    fixed = self._persistent_guard(runner, None)
-                    if fixed is not None:
-                        (actions, rnn_states), prev_actions, runner = fixed, fixed[0], None
-            else:
-                eager_once = False
-
-                def act_once(rs=rnn_states, pa=prev_actions, b=batch, m=not_done_masks):
-                    with torch.no_grad():
-                        return self.policy.act(b, rs, pa, m, deterministic=not config.EVAL.SAMPLE)
-
-                actions, rnn_new = act_once()
-                if depth_net.armed():
-                    torch.cuda.current_stream().synchronize()
-                    fixed = self._persistent_guard(None, act_once)
-                    if fixed is not None:
-                        actions, rnn_new = fixed
-                rnn_states = rnn_new
-                prev_actions.copy_(actions)
+            actions, rnn_states = stepper.step(batch, rnn_states, prev_actions, (not_done_masks,))
+            prev_actions = actions
             outputs = envs.step([a[0].item() for a in actions])
             observations, _, dones, infos = [list(x) for x in zip(*outputs)]
             not_done_masks = torch.tensor([[0] if done else [1] for done in dones], dtype=torch.uint8,
@@ -782,10 +774,11 @@ class BaseVLNCETrainer:
             observations, batch = self._batch(observations, not_done_masks, transform=not use_graph)
             next_episodes = envs.current_episodes()
             envs_to_pause = [i for i in range(envs.num_envs) if next_episodes[i].episode_id in stats_episodes]
-            if envs_to_pause and use_graph:
-                batch, runner, eager_once = self._map_before_pause(batch), None, True
+            if envs_to_pause:
+                batch = stepper.before_pause(batch)
             envs, rnn_states, not_done_masks, prev_actions, batch, _ = self._pause_envs(
                 envs_to_pause, envs, rnn_states, not_done_masks, prev_actions, batch)
+        stepper.close()
         self._check_mappers()
         tours = (envs.dtw_data(), envs.gt_paths()) if hasattr(envs, "dtw_data") else ({}, {})
         gathered = D.gather_objects((stats_episodes, tours))
@@ -814,18 +807,10 @@ class BaseVLNCETrainer:
         """base_il_trainer.py:258-311: drop the paused envs' rows from every per-env tensor and tell the policy
         (`net.delete_batch_idx`, the Latent-CMA tour memory) which rows went away."""
         if len(envs_to_pause) > 0:
-            state_index = list(range(envs.num_envs))
-            for idx in reversed(envs_to_pause):
-                state_index.pop(idx)
-                envs.pause_at(idx)
-            recurrent_hidden_states = recurrent_hidden_states[state_index]
-            agent_episode_not_done_masks = agent_episode_not_done_masks[state_index]
-            sim_episode_not_done_masks = sim_episode_not_done_masks[state_index]
-            tour_not_done_masks = tour_not_done_masks[state_index]
-            action_masks = action_masks[state_index]
-            prev_actions = prev_actions[state_index]
-            for k, v in batch.items():
-                batch[k] = v[state_index] if torch.is_tensor(v) else [v[i] for i in state_index]
+            state_index, (recurrent_hidden_states, agent_episode_not_done_masks, sim_episode_not_done_masks,
+                          tour_not_done_masks, action_masks, prev_actions) = self._compact_rows(
+                envs_to_pause, envs, (recurrent_hidden_states, agent_episode_not_done_masks, sim_episode_not_done_masks,
+                                      tour_not_done_masks, action_masks, prev_actions), batch)
             if rgb_frames is not None:
                 rgb_frames = [rgb_frames[i] for i in state_index]
             del_idxs_fn = getattr(self.policy.net, "delete_batch_idx", None)
@@ -867,18 +852,13 @@ class BaseVLNCETrainer:
         episodic_maps = self.config.EVAL.ITERATIVE_MAP_RESET == "episodic"
         envs = construct_envs(config, None, auto_reset_done=False, rank=self.rank, world=self.world, iterative=True)
         self._load_eval_policy(config, envs, config.IL.ckpt_to_load)
-        n = envs.num_envs
-        rnn_states = torch.zeros(n, self.policy.net.num_recurrent_layers, config.MODEL.STATE_ENCODER.hidden_size,
-                                 device=self.device)
-        prev_actions = torch.zeros(n, 1, device=self.device, dtype=torch.long)
-        agent_episode_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        sim_episode_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        tour_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        action_masks = torch.ones(n, 1, dtype=torch.uint8, device=self.device)
+        (rnn_states, prev_actions, agent_episode_not_done_masks, sim_episode_not_done_masks, tour_not_done_masks,
+         action_masks) = self._initial_state(config, envs.num_envs, iterative=True)
         # a captured step carries ONE policy mask (the agent-episode one, all MapCMA reads: quirk Q11) besides the
         # mapper's reset mask; policies with a tour memory read the tour mask too and run eagerly
         tour_policy = bool(config.MODEL.tour_memory or config.MODEL.tour_memory_variant)
         use_graph = self._graph_eligible() and not tour_policy
+        stepper = _PolicyStepper(self, True, use_graph, deterministic=not config.EVAL.SAMPLE)
 
         def make_batch(observations):
             reset_masks = agent_episode_not_done_masks if episodic_maps else tour_not_done_masks
@@ -891,37 +871,12 @@ class BaseVLNCETrainer:
         observations, batch = make_batch(observations)
         stats_tours = defaultdict(dict)  # tour id -> episode id -> stats
         dtw_data = defaultdict(list)     # tour id -> positions
-        runner, captured, eager_once = None, False, False
         t0 = time.time()
         while envs.num_envs > 0:
             current_episodes = envs.current_episodes()
-            if use_graph and not eager_once:
-                if runner is None:
-                    runner = self._make_runner(batch, rnn_states, prev_actions, first=not captured)
-                    captured = True
-                actions = runner.step(batch)
-                rnn_states, prev_actions = runner.rnn_states, actions
-                if depth_net.armed():
-                    torch.cuda.current_stream().synchronize()
-                    fixed = self._persistent_guard(runner, None)
-                    if fixed is not None:
-                        (actions, rnn_states), prev_actions, runner = fixed, fixed[0], None
-            else:
-                eager_once = False
-
-                def act_once(rs=rnn_states, pa=prev_actions, b=batch, m=(agent_episode_not_done_masks, sim_episode_not_done_masks,
-                                                                        tour_not_done_masks, action_masks)):
-                    with torch.no_grad():
-                        return self.policy.act_iterative(b, rs, pa, *m, deterministic=not config.EVAL.SAMPLE)
-
-                actions, rnn_new = act_once()
-                if depth_net.armed():
-                    torch.cuda.current_stream().synchronize()
-                    fixed = self._persistent_guard(None, act_once)
-                    if fixed is not None:
-                        actions, rnn_new = fixed
-                rnn_states = rnn_new
-                prev_actions.copy_(actions)
+            actions, rnn_states = stepper.step(batch, rnn_states, prev_actions, (
+                agent_episode_not_done_masks, sim_episode_not_done_masks, tour_not_done_masks, action_masks))
+            prev_actions = actions
             outputs = envs.step([a[0].item() for a in actions])
             (observations, _, agent_episode_dones, sim_episode_dones, tour_dones, produce_actions,
              infos) = [list(x) for x in zip(*outputs)]
@@ -947,12 +902,13 @@ class BaseVLNCETrainer:
             next_episodes = envs.current_episodes()
             envs_to_pause = [i for i in range(envs.num_envs)
                              if sim_episode_dones[i] and next_episodes[i].episode_id in stats_tours[next_episodes[i].tour_id]]
-            if envs_to_pause and use_graph:
-                batch, runner, eager_once = self._map_before_pause(batch), None, True
+            if envs_to_pause:
+                batch = stepper.before_pause(batch)
             (envs, rnn_states, agent_episode_not_done_masks, sim_episode_not_done_masks, tour_not_done_masks,
              action_masks, prev_actions, batch, _) = self._pause_iterative_envs(
                 envs_to_pause, envs, rnn_states, agent_episode_not_done_masks, sim_episode_not_done_masks,
                 tour_not_done_masks, action_masks, prev_actions, batch)
+        stepper.close()
         self._check_mappers()
         gt_local = envs.gt_paths() if hasattr(envs, "gt_paths") else {}
         gathered = D.gather_objects((dict(stats_tours), dict(dtw_data), gt_local))
@@ -1067,9 +1023,82 @@ class PrefetchLoader:
             th.join(timeout=5.0)
 
 
-class _RolloutStepper:
+class _PolicyStepper:
+    """The MI355X-native policy step of every rollout loop - the one place that decides how a step runs:
+      replayed  (`use_graph`) mapper + policy as captured hipGraphs, the state in the runner's buffers (`_make_runner`);
+      eager     `policy.act` / `act_iterative` on a batch the loop has mapped: every step without `use_graph`, and the ONE
+                step after a pause (`before_pause`), after which the smaller batch is captured again without executing;
+      guarded   a persistent depth-encoder launch that timed out voids the step: `guard`, after the caller's stream
+                synchronisation, computes it again (`_persistent_guard`) and drops a runner that holds the retired launch.
+    `deterministic` is how an eager step acts; a capture takes the arg-max (`_graph_eligible` rules sampling out) unless
+    `capture_deterministic` is False.  `extra_keys`: batch keys a capture reads besides the policy's own."""
+
+    def __init__(self, trainer, iterative, use_graph, deterministic, extra_keys=(), capture_deterministic=True):
+        self.tr, self.iterative, self.use_graph = trainer, iterative, use_graph
+        self.deterministic, self.capture_deterministic, self.extra_keys = deterministic, capture_deterministic, extra_keys
+        self.runner, self.captured, self.eager_once = None, False, False
+
+    def close(self):
+        self.runner = None
+
+    def before_pause(self, batch):
+        """Envs are about to pause (BaseVLNCETrainer._map_before_pause)."""
+        if self.use_graph:
+            batch = self.tr._map_before_pause(batch)
+            self.runner, self.eager_once = None, True
+        return batch
+
+    def _act(self, batch, rnn_states, prev_actions, masks):
+        pol = self.tr.policy
+        if self.iterative:
+            return pol.act_iterative(batch, rnn_states, prev_actions, *masks, deterministic=self.deterministic)
+        return pol.act(batch, rnn_states, prev_actions, masks[0], deterministic=self.deterministic)
+
+    def launch(self, batch, rnn_states, prev_actions, masks):
+        """Enqueue one step; no synchronisation.  masks: (not_done,) or the four iterative masks.
+        -> (actions, rnn_states, replayed?, act_once: the eager step again from the same inputs, for `guard`)"""
+        if self.use_graph and not self.eager_once:
+            if self.runner is None:
+                self.runner = self.tr._make_runner(batch, rnn_states, prev_actions, first=not self.captured,
+                                                   deterministic=self.capture_deterministic, extra_keys=self.extra_keys)
+                self.captured = True
+            actions = self.runner.step(batch)
+            return actions, self.runner.rnn_states, True, None
+        self.eager_once = False
+
+        def act_once():
+            with torch.no_grad():
+                return self._act(batch, rnn_states, prev_actions, masks)
+
+        return (*act_once(), False, act_once)
+
+    def guard(self, replayed, act_once):
+        """After the synchronisation that follows `launch`: None, or the step's (actions, rnn_states) computed again."""
+        fixed = self.tr._persistent_guard(self.runner if replayed else None, act_once)
+        if fixed is not None and replayed:
+            self.runner = None  # (its graphs contain the retired launch: the next step captures again)
+        return fixed
+
+    def step(self, batch, rnn_states, prev_actions, masks):
+        """One step of an eval loop -> (actions = the next step's `prev_actions`: the runner's buffer after a replay, the
+        carried tensor after an eager step; rnn_states).  Synchronises only while a persistent launch may be part of the
+        step (its time-out flag is read after the sync): else the env step's `.item()` stays the loop's only one."""
+        actions, rnn_states, replayed, act_once = self.launch(batch, rnn_states, prev_actions, masks)
+        if depth_net.armed():
+            torch.cuda.current_stream().synchronize()
+            fixed = self.guard(replayed, act_once)
+            if fixed is not None:
+                actions, rnn_states = fixed
+        if not replayed:
+            prev_actions.copy_(actions)
+            actions = prev_actions
+        return actions, rnn_states
+
+
+class _RolloutStepper(_PolicyStepper):
     """One sampled, expert-mixed policy step of a DAgger collection loop (dagger_trainer.py:416-427, 469-472;
-    iterative_collection_dagger_trainer.py:300-348) and the per-step host copies the loops store.
+    iterative_collection_dagger_trainer.py:300-348) and the per-step host copies the loops store, on `_PolicyStepper`'s
+    launch / guard lifecycle.
 
     Two ways to the same values:
       reference statements  `policy.act(...)` (torch's Categorical draw) then `where(rand < beta, expert, a)` and
@@ -1086,37 +1115,39 @@ class _RolloutStepper:
     host buffers together (the reference's hooks did a blocking `.cpu()` each)."""
 
     def __init__(self, trainer, beta, expert_uuid, iterative):
-        self.tr, self.beta, self.expert_uuid, self.iterative = trainer, float(beta), expert_uuid, iterative
         cfg, pol = trainer.config, trainer.policy
+        self.beta, self.expert_uuid = float(beta), expert_uuid
         self.dev = trainer.device
         self.on_gpu = self.dev.type == "cuda"
         self.device_mix = self.on_gpu and hasattr(pol, "U_SAMPLE")
+        use_graph = (self.device_mix and bool(getattr(cfg.IL.DAGGER, "USE_HIP_GRAPH", True))
+                     and trainer._graph_eligible(sampled=True) and type(pol).__name__ == "MapCMAPolicy")
+        super().__init__(trainer, iterative, use_graph, deterministic=False, extra_keys=(expert_uuid,),
+                         capture_deterministic=False)
         self.feats, self.hooks = trainer._feature_hooks(to_host=not self.on_gpu)
-        self.use_graph = (self.device_mix and bool(getattr(cfg.IL.DAGGER, "USE_HIP_GRAPH", True))
-                          and trainer._graph_eligible(sampled=True) and type(pol).__name__ == "MapCMAPolicy")
-        self.runner, self.captured, self.eager_once = None, False, False
         self.gen = torch.Generator().manual_seed(int(cfg.TASK_CONFIG.SEED) + 7919 * (trainer.rank + 1))
         self.pinned = {}
         if self.device_mix:
             pol.collect_mix = {"beta": self.beta, "expert_uuid": expert_uuid}
 
     def close(self):
+        super().close()
         for h in self.hooks:
             h.remove()
         if self.device_mix:
             self.tr.policy.collect_mix = None
 
-    def before_pause(self, batch):
-        """Envs are about to pause: a replaying loop maps the still uncompacted batch now, steps eagerly once and
-        captures again for the smaller batch afterwards (BaseVLNCETrainer._map_before_pause)."""
-        if self.use_graph:
-            batch = self.tr._map_before_pause(batch)
-            self.runner, self.eager_once = None, True
-        return batch
+    def _act(self, batch, rnn_states, prev_actions, masks):
+        a, r = super()._act(batch, rnn_states, prev_actions, masks)
+        if not self.device_mix:  # the reference's statements
+            expert = batch[self.expert_uuid].long()
+            a = torch.where(self.draw.to(a.device) < self.beta, expert, a)
+            a = torch.where(expert == -1, torch.zeros_like(a), a)
+        return a, r
 
     def _to_host(self, name, t):
         """Asynchronous D2H into a pinned buffer (one per name and shape); valid after the step's synchronise."""
-        if not self.on_gpu:
+        if t is None or not self.on_gpu:
             return t
         key = (name, tuple(t.shape), t.dtype)
         buf = self.pinned.get(key)
@@ -1131,57 +1162,32 @@ class _RolloutStepper:
         int), `occ` / `sem` (numpy or None), `depth` / `rgb` (CPU tensors or None))."""
         tr, pol = self.tr, self.tr.policy
         n = prev_actions.shape[0]
-        draw = torch.rand((n, 1), dtype=torch.float)  # default generator: the reference's rand_like(actions)
+        self.draw = torch.rand((n, 1), dtype=torch.float)  # default generator: the reference's rand_like(actions)
         if self.device_mix:
             batch[pol.U_SAMPLE] = torch.rand((n, 1), dtype=torch.float, generator=self.gen).to(self.dev)
-            batch[pol.U_BETA] = draw.to(self.dev)
-        replayed = self.use_graph and not self.eager_once
+            batch[pol.U_BETA] = self.draw.to(self.dev)
+        actions, rnn_states, replayed, act_once = self.launch(batch, rnn_states, prev_actions, masks)
         if replayed:
-            if self.runner is None:
-                self.runner = tr._make_runner(batch, rnn_states, prev_actions, first=not self.captured,
-                                              deterministic=False, extra_keys=(self.expert_uuid,))
-                self.captured = True
-            runner = self.runner
-            actions = runner.step(batch)
-            rnn_states = runner.rnn_states
-            occ, sem = runner.maps()
-            depth = runner.depth_features() if tr._caches_depth() else None
+            occ, sem = self.runner.maps()
+            depth = self.runner.depth_features() if tr._caches_depth() else None
             rgb = None
         else:
-            self.eager_once = False
-            rnn_in = rnn_states
-
-            def act_once():
-                if self.iterative:
-                    a, r = pol.act_iterative(batch, rnn_in, prev_actions, *masks, deterministic=False)
-                else:
-                    a, r = pol.act(batch, rnn_in, prev_actions, masks[0], deterministic=False)
-                if not self.device_mix:  # the reference's statements
-                    expert = batch[self.expert_uuid].long()
-                    a = torch.where(draw.to(a.device) < self.beta, expert, a)
-                    a = torch.where(expert == -1, torch.zeros_like(a), a)
-                return a, r
-
-            actions, rnn_states = act_once()
             occ, sem = batch.get("occupancy_map"), batch.get("semantic_map")
             depth, rgb = self.feats.get("depth"), self.feats.get("rgb")
         if (occ is None) != (sem is None):
             raise RuntimeError("either both map keys should exist in the batch or neither")
 
         def host_copies():
-            return {"actions": self._to_host("a", actions), "occ": None if occ is None else self._to_host("o", occ),
-                    "sem": None if sem is None else self._to_host("s", sem),
-                    "depth": None if depth is None else self._to_host("d", depth),
-                    "rgb": None if rgb is None else self._to_host("r", rgb)}
+            return {k: self._to_host(k, t) for k, t in (("actions", actions), ("occ", occ), ("sem", sem), ("depth", depth),
+                                                        ("rgb", rgb))}
 
         host = host_copies()
         if self.on_gpu:
             torch.cuda.current_stream().synchronize()
-            fixed = tr._persistent_guard(runner if replayed else None, None if replayed else act_once) if depth_net.armed() else None
+            fixed = self.guard(replayed, act_once) if depth_net.armed() else None
             if fixed is not None:  # a persistent kernel of this step timed out: the values above are void, these are the step's
                 actions, rnn_states = fixed
                 if replayed:
-                    self.runner = None  # (its graphs contain the retired launch: the next step captures again)
                     depth = self.feats.get("depth") if tr._caches_depth() else None  # (the redo ran eagerly: the encoder's hook kept them)
                 else:
                     depth, rgb = self.feats.get("depth"), self.feats.get("rgb")
@@ -1282,10 +1288,7 @@ class DaggerTrainer(BaseVLNCETrainer):
         envs = construct_envs(cfg, None, rank=self.rank, world=self.world, iterative=False)
         expert_uuid = cfg.IL.DAGGER.expert_policy_sensor_uuid
         n = envs.num_envs
-        rnn_states = torch.zeros(n, self.policy.net.num_recurrent_layers, cfg.MODEL.STATE_ENCODER.hidden_size,
-                                 device=self.device)
-        prev_actions = torch.zeros(n, 1, device=self.device, dtype=torch.long)
-        not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
+        rnn_states, prev_actions, not_done_masks = self._initial_state(cfg, n)
         p = cfg.IL.DAGGER.p
         beta = 0.0 if p == 0.0 else p ** data_it
         ensure_unique_episodes = beta == 1.0
@@ -1347,8 +1350,7 @@ class DaggerTrainer(BaseVLNCETrainer):
                         o.pop("depth", None)
                     if host["occ"] is not None:
                         o["occupancy_map"], o["semantic_map"] = host["occ"][i], host["sem"][i]
-                        for k in ["semantic", "semantic12", "world_robot_pose", "world_robot_orientation", "env_name",
-                                  "rgb"]:
+                        for k in MAP_SOURCE_KEYS + ("rgb",):
                             o.pop(k, None)
                     episodes[i].append((o, prev_host[i], experts[i], tours_now[i]))
                 skips = [int(e) == -1 for e in experts]
@@ -1432,18 +1434,15 @@ class IterativeCollectionDaggerTrainer(DaggerTrainer):
     "0" and the trajectories are numbered from 1 (:228-235, 377-385).  Pinned to runs of the reference's own
     `_update_dataset` on a scripted iterative env (tests/golden/iterative_golden.json, "collect")."""
 
-    def add_map_to_observations(self, observations, batch, num_envs):
-        """:28-58: copy this step's maps into the per-env observation dicts (what gets stored) and drop the keys
-        that only served to build them."""
-        map_k_sum = int("occupancy_map" in batch) + int("semantic_map" in batch)
-        if map_k_sum == 1:
-            raise RuntimeError("either both map keys should exist in the batch or neither")
-        if map_k_sum != 2:
+    def add_map_to_observations(self, observations, occ, sem, num_envs):
+        """:28-58: copy this step's maps - the step's host copies; `_RolloutStepper.step` has raised unless both exist or
+        neither (None) - into the per-env observation dicts (what gets stored) and drop the keys that only served to
+        build them."""
+        if occ is None:
             return observations
-        occ, sem = batch["occupancy_map"].cpu().numpy(), batch["semantic_map"].cpu().numpy()
         for i in range(num_envs):
             observations[i]["occupancy_map"], observations[i]["semantic_map"] = occ[i], sem[i]
-            for k in ["semantic", "semantic12", "world_robot_pose", "world_robot_orientation", "env_name"]:
+            for k in MAP_SOURCE_KEYS:
                 observations[i].pop(k, None)
         return observations
 
@@ -1457,13 +1456,8 @@ class IterativeCollectionDaggerTrainer(DaggerTrainer):
         envs = construct_envs(cfg, None, rank=self.rank, world=self.world, iterative=True)
         expert_uuid = cfg.IL.DAGGER.expert_policy_sensor_uuid
         n = envs.num_envs
-        rnn_states = torch.zeros(n, self.policy.net.num_recurrent_layers, cfg.MODEL.STATE_ENCODER.hidden_size,
-                                 device=self.device)
-        prev_actions = torch.zeros(n, 1, device=self.device, dtype=torch.long)
-        agent_episode_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        sim_episode_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        tour_not_done_masks = torch.zeros(n, 1, dtype=torch.uint8, device=self.device)
-        action_masks = torch.ones(n, 1, dtype=torch.uint8, device=self.device)
+        (rnn_states, prev_actions, agent_episode_not_done_masks, sim_episode_not_done_masks, tour_not_done_masks,
+         action_masks) = self._initial_state(cfg, n, iterative=True)
         p = cfg.IL.DAGGER.p
         beta = 0.0 if p == 0.0 else p ** data_it  # in Python 0.0 ** 0.0 == 1.0, but we want 0.0
         ensure_unique_episodes = beta == 1.0
@@ -1546,11 +1540,7 @@ class IterativeCollectionDaggerTrainer(DaggerTrainer):
                 actions, rnn_states, host = stepper.step(
                     batch, rnn_states, prev_actions,
                     (agent_episode_not_done_masks, sim_episode_not_done_masks, tour_not_done_masks, action_masks))
-                if host["occ"] is not None:  # add_map_to_observations (:28-58) from the step's host copies
-                    for i in range(envs.num_envs):
-                        observations[i]["occupancy_map"], observations[i]["semantic_map"] = host["occ"][i], host["sem"][i]
-                        for k in ["semantic", "semantic12", "world_robot_pose", "world_robot_orientation", "env_name"]:
-                            observations[i].pop(k, None)
+                observations = self.add_map_to_observations(observations, host["occ"], host["sem"], envs.num_envs)
                 for i, current_episode in enumerate(envs.current_episodes()):
                     if not acting[i]:  # only add steps if the agent is acting: skip oracle phases
                         continue
