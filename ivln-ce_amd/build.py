@@ -21,6 +21,7 @@ SOURCES = {
     "conv_bf3.hip": [],
     "gn_conv.hip": [],
     "depth_net.hip": [],
+    "group_conv.hip": [],
     "cma_step.hip": [],
     "state_rnn.hip": [],
     # (GRU instruction encoder: its register arrays are indexed by fully unrolled loops only - 0 scratch bytes)
@@ -61,6 +62,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_train.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_augment.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_tour_state.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_depth_backbones.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

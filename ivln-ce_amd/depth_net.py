@@ -227,6 +227,8 @@ def supported(encoder):
                     ok = ok and all(c[i].num_groups == 16 for i in (1, 4, 7)) and all(c[i].bias is None for i in (0, 3, 6))
                     ok = ok and (blk.downsample is None or (blk.downsample[0].kernel_size == (1, 1) and blk.downsample[1].num_groups == 16))
                     ok = ok and (blk.downsample is not None) == (bi == 0)
+                    # a grouped 3x3 conv (ResNeXt) or an SE branch has the same conv shapes and no form in the kernel
+                    ok = ok and c[3].groups == 1 and getattr(blk, "se", None) is None
             comp, gcomp = encoder.compression[0], encoder.compression[1]
             ok = bool(ok and comp.kernel_size == (3, 3) and comp.in_channels == 1024 and gcomp.num_groups == 1)
         except (AttributeError, IndexError, TypeError):

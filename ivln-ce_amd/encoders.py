@@ -365,25 +365,75 @@ def _conv(cin, cout, k, stride=1, pad=0):
     return nn.Conv2d(cin, cout, kernel_size=k, stride=stride, padding=pad, bias=False)
 
 
+# MODEL.DEPTH_ENCODER.backbone (resnet_encoders.py:41 hands the key to getattr(resnet, backbone)): name -> (blocks per
+# layer, ResNeXt bottlenecks, squeeze-and-excite tails) of habitat-lab v0.1.7 rl/ddppo/policy/resnet.py
+DEPTH_BACKBONES = {
+    "resnet50": ((3, 4, 6, 3), False, False),
+    "resneXt50": ((3, 4, 6, 3), True, False),
+    "se_resnet50": ((3, 4, 6, 3), False, True),
+    "se_resneXt50": ((3, 4, 6, 3), True, True),
+    "se_resneXt101": ((3, 4, 23, 3), True, True),
+}
+
+
+def depth_backbone_spec(backbone):
+    """-> (blocks per layer, resneXt, se); ValueError for any other name (resnet18 has another block and is not built)."""
+    spec = DEPTH_BACKBONES.get(backbone)
+    if spec is None:
+        raise ValueError(f"MODEL.DEPTH_ENCODER.backbone must be one of {', '.join(DEPTH_BACKBONES)}; got {backbone!r}")
+    return spec
+
+
+class _SE(nn.Module):
+    """habitat-lab's SE branch: squeeze = global average pool, excite = Linear(C, C/r) - ReLU - Linear(C/r, C) - Sigmoid.
+    The HIP path never calls it as a module: ops.se_gate reads its parameters (state-dict keys se.excite.{0,2}.*)."""
+
+    def __init__(self, planes, r=16):
+        super().__init__()
+        self.squeeze = nn.AdaptiveAvgPool2d(1)
+        self.excite = nn.Sequential(nn.Linear(planes, int(planes / r)), nn.ReLU(True), nn.Linear(int(planes / r), planes),
+                                    nn.Sigmoid())
+
+
 class _Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, ngroups, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, ngroups, stride=1, downsample=None, expansion=4, cardinality=1, se=False):
         super().__init__()
+        self.expansion = expansion
         self.convs = nn.Sequential(
             _conv(inplanes, planes, 1), nn.GroupNorm(ngroups, planes), nn.ReLU(True),
-            _conv(planes, planes, 3, stride, 1), nn.GroupNorm(ngroups, planes), nn.ReLU(True),
-            _conv(planes, planes * 4, 1), nn.GroupNorm(ngroups, planes * 4),
+            nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False, groups=cardinality),
+            nn.GroupNorm(ngroups, planes), nn.ReLU(True),
+            _conv(planes, planes * expansion, 1), nn.GroupNorm(ngroups, planes * expansion),
         )
+        if se:
+            self.se = _SE(planes * expansion)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
+
+    @property
+    def plain(self):
+        """The ResNet-50 bottleneck: dense 3x3 conv, no SE branch - what the chain, nconv, persistent and training forms
+        are written for.  Anything else runs the conv + GroupNorm pair form only."""
+        return self.convs[3].groups == 1 and getattr(self, "se", None) is None
 
     def forward_hip(self, x):
         """conv -> GroupNorm(+ReLU) pairs: the conv leaves raw (split-K) slabs in the workspace and the
         GroupNorm kernel reduces + normalises them, 2 launches per pair."""
         c = self.convs
         y, ds = self.body_hip(x)
+        se = getattr(self, "se", None)
+        if se is not None:
+            # SE tail, two launches: the gate from the raw conv3 output and GroupNorm 3's statistics, then
+            # relu(gate * GroupNorm3 + identity) in place of the block's last GroupNorm launch
+            e, g3 = se.excite, c[7]
+            gate = ops.se_gate(y, g3.weight, g3.bias, g3.num_groups, g3.eps, e[0].weight, e[0].bias, e[2].weight, e[2].bias)
+            if ds is not None:
+                gn = self.downsample[1]
+                return ops.se_apply(y, g3.weight, g3.bias, g3.num_groups, g3.eps, gate, x2=ds, gamma2=gn.weight, beta2=gn.bias)
+            return ops.se_apply(y, g3.weight, g3.bias, g3.num_groups, g3.eps, gate, residual=x)
         if ds is not None:
             gn = self.downsample[1]
             return ops.groupnorm(y, c[7].weight, c[7].bias, c[7].num_groups, c[7].eps, relu=True, x2=ds,
@@ -403,7 +453,10 @@ class _Bottleneck(nn.Module):
             ds = ops.conv2d(x, self.downsample[0].weight, stride=self.stride, defer=True, ws_slot=1)
         y = ops.conv2d(x, c[0].weight, defer=True)
         y = ops.groupnorm(y, c[1].weight, c[1].bias, c[1].num_groups, c[1].eps, relu=True)
-        y = ops.conv2d(y, c[3].weight, stride=self.stride, pad=1, defer=True)
+        if c[3].groups == 1:
+            y = ops.conv2d(y, c[3].weight, stride=self.stride, pad=1, defer=True)
+        else:  # ResNeXt: the grouped 3x3 conv leaves a plain tensor, which the same GroupNorm launch takes
+            y = ops.gconv3x3(y, c[3].weight, c[3].groups, stride=self.stride)
         y = ops.groupnorm(y, c[4].weight, c[4].bias, c[4].num_groups, c[4].eps, relu=True)
         return ops.conv2d(y, c[6].weight, defer=True), ds
 
@@ -439,30 +492,46 @@ def _gn_train(raw, gn, relu, residual=None):
 
 
 class _ResNet50GN(nn.Module):
-    def __init__(self, in_channels, base_planes, ngroups):
+    """habitat-lab's GroupNorm ResNet: ResNet-50 by default; `layers`, `resnext` and `se` make the other DD-PPO backbones
+    (DEPTH_BACKBONES).  ResNeXt: expansion 2, the four layers on doubled planes (the stem keeps `base_planes`), 3x3 convs
+    with cardinality = base_planes / 2 groups, in every block of a layer."""
+
+    def __init__(self, in_channels, base_planes, ngroups, layers=(3, 4, 6, 3), resnext=False, se=False):
         super().__init__()
+        self.expansion = 2 if resnext else 4
+        self.cardinality = int(base_planes / 2) if resnext else 1
+        self.has_se = bool(se)
         self.conv1 = nn.Sequential(
             nn.Conv2d(in_channels, base_planes, kernel_size=7, stride=2, padding=3, bias=False),
             nn.GroupNorm(ngroups, base_planes), nn.ReLU(True),
         )
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         self.inplanes = base_planes
-        self.layer1 = self._make_layer(ngroups, base_planes, 3)
-        self.layer2 = self._make_layer(ngroups, base_planes * 2, 4, stride=2)
-        self.layer3 = self._make_layer(ngroups, base_planes * 4, 6, stride=2)
-        self.layer4 = self._make_layer(ngroups, base_planes * 8, 3, stride=2)
+        if resnext:
+            base_planes *= 2
+        self.layer1 = self._make_layer(ngroups, base_planes, layers[0])
+        self.layer2 = self._make_layer(ngroups, base_planes * 2, layers[1], stride=2)
+        self.layer3 = self._make_layer(ngroups, base_planes * 4, layers[2], stride=2)
+        self.layer4 = self._make_layer(ngroups, base_planes * 8, layers[3], stride=2)
         self.final_channels = self.inplanes
         self.final_spatial_compress = 1.0 / (2 ** 5)
 
     def _make_layer(self, ngroups, planes, blocks, stride=1):
         downsample = None
-        if stride != 1 or self.inplanes != planes * 4:
-            downsample = nn.Sequential(_conv(self.inplanes, planes * 4, 1, stride), nn.GroupNorm(ngroups, planes * 4))
-        layers = [_Bottleneck(self.inplanes, planes, ngroups, stride, downsample)]
-        self.inplanes = planes * 4
+        ex = self.expansion
+        kw = dict(expansion=ex, cardinality=self.cardinality, se=self.has_se)
+        if stride != 1 or self.inplanes != planes * ex:
+            downsample = nn.Sequential(_conv(self.inplanes, planes * ex, 1, stride), nn.GroupNorm(ngroups, planes * ex))
+        layers = [_Bottleneck(self.inplanes, planes, ngroups, stride, downsample, **kw)]
+        self.inplanes = planes * ex
         for _ in range(1, blocks):
-            layers.append(_Bottleneck(self.inplanes, planes, ngroups))
+            layers.append(_Bottleneck(self.inplanes, planes, ngroups, **kw))
         return nn.Sequential(*layers)
+
+    @property
+    def plain(self):
+        """Every block is the ResNet-50 bottleneck (dense 3x3 conv, no SE): the chain, persistent and training forms apply."""
+        return all(b.plain for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer)
 
     def forward_chain(self, x, tail):
         """The whole backbone as a chain of ops.gn_conv launches: every GroupNorm kernel also computes its slice of
@@ -470,6 +539,8 @@ class _ResNet50GN(nn.Module):
         `tail` = (weight, stride, pad) of the conv that follows the backbone (the encoder's compression conv).
         Returns that conv's raw output (a `Deferred`), or None when a shape is outside the kernel's envelope."""
         blocks = [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer]
+        if not self.plain:  # a grouped conv or an SE gate: the chain's kernels have neither (the caller runs the pairs)
+            return None
 
         def feeds(blk):  # what the kernel that produces `blk`'s input has to emit for it
             ds = None if blk.downsample is None else (blk.downsample[0].weight, blk.stride)
@@ -599,15 +670,20 @@ class _ResNet50GN(nn.Module):
 
 
 class ResNetEncoder(nn.Module):
-    """habitat-lab ResNetEncoder for a depth-only observation space: avg_pool2d(2) -> GN-ResNet50 ->
-    3x3 compression conv + GroupNorm(1) + ReLU -> (B,128,4,4)."""
+    """habitat-lab ResNetEncoder for a depth-only observation space: avg_pool2d(2) -> GN-ResNet50 (or another DD-PPO
+    `backbone`, DEPTH_BACKBONES) -> 3x3 compression conv + GroupNorm(1) + ReLU -> (B,128,4,4)."""
 
-    def __init__(self, depth_shape, baseplanes=32, ngroups=16):
+    def __init__(self, depth_shape, baseplanes=32, ngroups=16, backbone="resnet50"):
         super().__init__()
+        layers, resnext, se = depth_backbone_spec(backbone)
+        self.backbone_name = backbone
         spatial_size = depth_shape[0] // 2
         self._n_input_depth = depth_shape[2]
         self.running_mean_and_var = nn.Sequential()
-        self.backbone = _ResNet50GN(self._n_input_depth, baseplanes, ngroups)
+        if backbone == "resnet50":
+            self.backbone = _ResNet50GN(self._n_input_depth, baseplanes, ngroups)
+        else:
+            self.backbone = _ResNet50GN(self._n_input_depth, baseplanes, ngroups, layers=layers, resnext=resnext, se=se)
         final_spatial = int(spatial_size * self.backbone.final_spatial_compress)
         num_compression_channels = int(round(2048 / (final_spatial ** 2)))
         self.compression = nn.Sequential(
@@ -692,11 +768,16 @@ class VlnResnetDepthEncoder(nn.Module):
                  resnet_baseplanes: int = 32, normalize_visual_inputs: bool = False, trainable: bool = False,
                  spatial_output: bool = False) -> None:
         super().__init__()
-        assert backbone == "resnet50" and not normalize_visual_inputs and spatial_output
+        assert not normalize_visual_inputs and spatial_output
+        depth_backbone_spec(backbone)  # (ValueError that lists the accepted names)
+        if trainable and backbone != "resnet50":
+            raise ValueError(f"MODEL.DEPTH_ENCODER.trainable needs backbone resnet50 (the HIP backward walks ResNet-50 "
+                             f"bottlenecks only); got {backbone!r}")
         depth_shape = observation_space.spaces["depth"].shape
         if len(depth_shape) == 4:  # single_frame_box_shape (common/utils.py:38-48)
             depth_shape = depth_shape[1:]
-        self.visual_encoder = ResNetEncoder(depth_shape, baseplanes=resnet_baseplanes, ngroups=resnet_baseplanes // 2)
+        self.visual_encoder = ResNetEncoder(depth_shape, baseplanes=resnet_baseplanes, ngroups=resnet_baseplanes // 2,
+                                            backbone=backbone)
         for param in self.visual_encoder.parameters():
             param.requires_grad_(trainable)
         if checkpoint != "NONE":

@@ -903,6 +903,92 @@ def groupnorm(x, gamma, beta, groups, eps=1e-5, relu=False, residual=None, out=N
     return out
 
 
+# ---- depth backbones beyond ResNet-50 (include/ivln_depth_backbones.h, csrc/group_conv.hip) ---------------------------
+_dbsigs_done = False
+
+
+def _DB():
+    """Bindings of include/ivln_depth_backbones.h (csrc/group_conv.hip)."""
+    global _dbsigs_done
+    L = _L()
+    if not _dbsigs_done:
+        L.ivln_gconv3x3_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, vp]
+        L.ivln_se_gate_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, i64, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp]
+        L.ivln_se_apply_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i64, i64, i32, i64, i64, i64, vp, vp,
+                                        vp, i64, i64, i32, i64, vp]
+        _dbsigs_done = True
+    return L
+
+
+def _gn_operand(x):
+    """A GroupNorm input the way the kernels address it: an NCHW tensor or a `Deferred` conv output ->
+    (pointer, N, C, H, W, image stride, channel stride, slabs, slab stride, device)."""
+    if isinstance(x, Deferred):
+        HW = x.H * x.W
+        return dptr(x.ws), x.N, x.C, x.H, x.W, HW, x.N * HW, x.splits, x.C * x.N * HW, x.ws.device
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.IvlnError("a GroupNorm operand is a contiguous fp32 NCHW tensor or a Deferred conv output")
+    N, Cc, H, W = x.shape
+    return _p(x), N, Cc, H, W, 0, 0, 1, 0, x.device
+
+
+def gconv3x3(x, w, groups, stride=1, in_img_stride=0, out=None):
+    """Grouped 3x3 conv, pad 1, stride 1 | 2, as many output as input channels (the ResNeXt bottleneck's middle conv):
+    x (N, C, H, W) [an image's planes dense, images `in_img_stride` floats apart], w (C, C/groups, 3, 3) -> a plain
+    (N, C, Ho, Wo) tensor, which `groupnorm` takes as it is."""
+    N, Cc, H, W = x.shape
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or not w.is_contiguous():
+        raise _lib.IvlnError("gconv3x3: fp32 operands, dense weights")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != Cc:
+        raise _lib.IvlnError(f"gconv3x3: weights {tuple(w.shape)} are not (C, C/groups, 3, 3) for C = {Cc}")
+    if groups > 0 and Cc % groups == 0 and w.shape[1] != Cc // groups:  # (what the library reads; the rest it refuses itself)
+        raise _lib.IvlnError(f"gconv3x3: weights {tuple(w.shape)} do not hold {Cc // groups} channels per group")
+    if in_img_stride == 0 and not x.is_contiguous():
+        raise _lib.IvlnError("gconv3x3: a strided input passes its image stride")
+    s = max(int(stride), 1)
+    if out is None:
+        out = torch.empty((N, Cc, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device)
+    check(_DB().ivln_gconv3x3_f32(_p(x), dptr(w), dptr(out), N, Cc, H, W, groups, stride, in_img_stride, stream_ptr()),
+          "ivln_gconv3x3_f32")
+    return out
+
+
+def se_gate(x, gamma, beta, groups, eps, w1, b1, w2, b2, out=None):
+    """The squeeze-and-excite gate of GroupNorm(x) without materialising it: x an NCHW tensor or a `Deferred` conv
+    output -> (N, C) = sigmoid(w2 . relu(w1 . mean_hw(GroupNorm(x)) + b1) + b2).  One launch for the batch."""
+    xp, N, Cc, H, W, x_img, x_chan, splits, slab, dev = _gn_operand(x)
+    Cr = w1.shape[0]
+    if tuple(w1.shape) != (Cr, Cc) or tuple(w2.shape) != (Cc, Cr) or b1.numel() != Cr or b2.numel() != Cc:
+        raise _lib.IvlnError(f"se_gate: excite weights {tuple(w1.shape)} / {tuple(w2.shape)} do not fit {Cc} channels")
+    if out is None:
+        out = torch.empty((N, Cc), dtype=torch.float32, device=dev)
+    check(_DB().ivln_se_gate_f32(xp, dptr(gamma), dptr(beta), N, Cc, H * W, groups, eps, x_img, x_chan, splits, slab,
+                                 dptr(w1), dptr(b1), dptr(w2), dptr(b2), Cr, dptr(out), stream_ptr()), "ivln_se_gate_f32")
+    return out
+
+
+def se_apply(x, gamma, beta, groups, eps, gate, residual=None, x2=None, gamma2=None, beta2=None, out=None, y_img_stride=0,
+             r_img_stride=0):
+    """relu(gate[n, c] * GroupNorm(x) + identity): the SE bottleneck's tail.  x / x2 as `groupnorm` takes them (NCHW or
+    `Deferred`); identity = `residual` (a tensor) or GroupNorm(x2; gamma2, beta2), exactly one of the two."""
+    xp, N, Cc, H, W, x_img, x_chan, splits, slab, dev = _gn_operand(x)
+    HW = H * W
+    if out is None:
+        out = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
+    if gate.numel() != N * Cc:
+        raise _lib.IvlnError("se_apply: the gate holds N * C values")
+    x2p, x2_img, x2_chan, splits2, slab2, g2, b2 = None, 0, 0, 1, 0, None, None
+    if x2 is not None:
+        x2p, N2, C2, H2, W2, x2_img, x2_chan, splits2, slab2, _ = _gn_operand(x2)
+        if (N2, C2, H2, W2) != (N, Cc, H, W):
+            raise _lib.IvlnError("se_apply: the second operand has another shape")
+        g2, b2 = dptr(gamma2), dptr(beta2)
+    check(_DB().ivln_se_apply_f32(xp, dptr(gamma), dptr(beta), dptr(gate), _p(residual), _p(out), N, Cc, HW, groups, eps,
+                                  x_img, x_chan, splits, slab, y_img_stride, r_img_stride, x2p, g2, b2, x2_img, x2_chan,
+                                  splits2, slab2, stream_ptr()), "ivln_se_apply_f32")
+    return out
+
+
 IVLN_E_UNSUPPORTED = -5
 
 
