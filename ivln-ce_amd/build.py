@@ -63,6 +63,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_seg_augment.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_tour_state.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_depth_backbones.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_conv_ks_waves.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

@@ -19,6 +19,7 @@
 
 #include "bf3_common.h"
 #include "residency.h"
+#include "../../include/ivln_conv_ks_waves.h"
 
 namespace {
 
@@ -491,17 +492,22 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_bf3(const ivln_gemm_de
 // KS = 2: the same kernel for the stacked parity classes of a stride-2 3x3 transposed conv over few pixels (the decoder's first
 // upsampling stages, rednet.py:152-181 at 8 x 8 and 16 x 16): rows = 4 * channel + class, a 2 x 2 window, and an epilogue that
 // stores 2 x 2 output blocks (IVLN_D_NCHW_UP2X4).
-template <int PTH, int PTW, int TN = 2, int KS = 3>
-__global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, const unsigned char* a_split, long long a_grp_bytes,
+// NW = 4 (two workgroups of four waves on a CU instead of two rounds of one eight-wave workgroup: DESIGN.md section 3,
+// "co-resident K-split workgroups"): the same K over four waves, twice the chunks per wave, half the LDS - for the grids
+// with more workgroups than CUs and at most twice as many, where every workgroup then starts at once and a CU pays the
+// prologue, the reduction barrier and the epilogue once.  The K loop is the same code; the sum over K is four partial
+// tiles in a fixed order (not bit-equal to NW = 8).
+template <int PTH, int PTW, int TN = 2, int KS = 3, int NW = 8>
+__global__ __launch_bounds__(64 * NW, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, const unsigned char* a_split, long long a_grp_bytes,
                                                         int tiles_w, int tiles_h, int nimg) {
     // DA: weight taps in flight.  A tap is only 12 MFMAs here (384 pipe cycles, 768 with the SIMD's other wave): three taps
     // ahead were ~1 us of cover against an L2 round trip of 1-2 us under load - every tap waited (first version: 28 us for
     // 512 x 512 x 4608 with 13 us of MFMA issue).  A whole chunk ahead (9 taps, 108 registers) covers it.
     // TN = 1 (32 pixels per workgroup): the launches that fill less than half the chip with 64-pixel tiles (512 x 512 x 4608:
     // 128 workgroups) - twice the workgroups, half the MFMAs per wave, 20 % more halo per output.
-    constexpr int NW = 8, KK = KS * KS, DA = KK;
+    constexpr int KK = KS * KS, DA = KK, BS = 64 * NW;
     constexpr bool UP = KS == 2;
-    static_assert(PTH * PTW == 32 * TN && (KS == 3 || KS == 2), "32 TN pixels per workgroup");
+    static_assert(PTH * PTW == 32 * TN && (KS == 3 || KS == 2) && (NW == 8 || NW == 4), "32 TN pixels per workgroup, 8 or 4 waves");
     constexpr int PH = PTH + KS - 1, PWR = PTW + KS - 1, NPIX = PH * PWR;
     constexpr int WREG = (NPIX * PIXB + 15) & ~15;  // bytes of a wave's patch region
     constexpr int LDT = 32 * TN + 4;
@@ -593,7 +599,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
             }
         }
     }
-    // ---- the eight partial tiles meet in LDS: red[wave][32 channels][64 pixels (+4)] over the patch regions ----
+    // ---- the NW partial tiles meet in LDS: red[wave][32 channels][64 pixels (+4)] over the patch regions (a wave with an empty
+    // slice brings zeros); the items below go over the workgroup's 64 NW threads in passes ----
 #ifdef BF3_TIMING
     const unsigned long long ts2 = lane == 0 ? wall_clock64() : 0ull;
 #endif
@@ -604,8 +611,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
     if constexpr (UP) {
         // 8 channels x 2 rows of the 2 x 2 blocks x 16 TN pixel pairs: GEMM rows 4 c + 2 a (b = 0) and + 1 (b = 1) at two
         // horizontally adjacent pixels = four consecutive floats of output row 2 ho + a
-        if (t < 16 * 16 * TN) {
-            const int r = t / (16 * TN), j = t % (16 * TN);
+#pragma unroll
+        for (int it = 0; it < (16 * 16 * TN + BS - 1) / BS; ++it) {
+            const int item = t + it * BS;
+            if (item >= 16 * 16 * TN) break;
+            const int r = item / (16 * TN), j = item % (16 * TN);
             const int ml = 2 * r, nl = 2 * j;
             const int ph = nl / PTW, pw = nl % PTW;
             const int ho = ho0 + ph, wo = wo0 + pw;
@@ -617,15 +627,20 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
                 bf3_quad_store(p, v, addr, co);
             }
         }
-    } else if (t < 32 * 8 * TN) {
-        const int ml = t / (8 * TN), c4 = t % (8 * TN);  // 32 channels x 8 TN pixel quads
-        const int m = m0 + ml, nl = 4 * c4;
-        const int ph = nl / PTW, pw = nl % PTW;
-        const int ho = ho0 + ph, wo = wo0 + pw;
-        float4 v = bf3_red_sum<NW, LDT, float4>(red + ml * LDT + nl);
-        if (m < p.M && img0 < nimg && ho < p.Hout && wo < p.Wout) {
-            const int64_t addr = ((int64_t)img0 * p.Ctot + m) * p.HoWo + ho * p.Wout + wo;
-            bf3_quad_store(p, v, addr, p.grp_imgs > 0 ? (img0 / p.grp_imgs) * p.M + m : m);
+    } else {
+#pragma unroll
+        for (int it = 0; it < (32 * 8 * TN + BS - 1) / BS; ++it) {
+            const int item = t + it * BS;
+            if (item >= 32 * 8 * TN) break;
+            const int ml = item / (8 * TN), c4 = item % (8 * TN);  // 32 channels x 8 TN pixel quads
+            const int m = m0 + ml, nl = 4 * c4;
+            const int ph = nl / PTW, pw = nl % PTW;
+            const int ho = ho0 + ph, wo = wo0 + pw;
+            float4 v = bf3_red_sum<NW, LDT, float4>(red + ml * LDT + nl);
+            if (m < p.M && img0 < nimg && ho < p.Hout && wo < p.Wout) {
+                const int64_t addr = ((int64_t)img0 * p.Ctot + m) * p.HoWo + ho * p.Wout + wo;
+                bf3_quad_store(p, v, addr, p.grp_imgs > 0 ? (img0 / p.grp_imgs) * p.M + m : m);
+            }
         }
     }
 #ifdef BF3_TIMING
@@ -642,21 +657,43 @@ __global__ __launch_bounds__(512, 2) void k_conv_bf3_ks(const ivln_gemm_desc p, 
 #endif
 }
 
-template <int PTH, int PTW, int TN = 2, int KS = 3>
+// launches of the two K-split kernels by wave count since the last reset (ivln_conv_ks_waves): [0] k_conv_bf3_ks with 8 waves,
+// [1] with 4, [2] k_conv1x1_bf3_ks' K-split form with 8 waves, [3] with 4.  Host-side tally, not thread-safe.
+static long long g_bf3_ks_waves[4] = {0, 0, 0, 0};
+
+template <int PTH, int PTW, int TN = 2, int KS = 3, int NW = 8>
 int launch_bf3_ks_tile(const ivln_gemm_desc& d, hipStream_t s, const unsigned char* a_split, int64_t grp_bytes, int nimg) {
-    constexpr int NPIX = (PTH + KS - 1) * (PTW + KS - 1), WREG = (NPIX * PIXB + 15) & ~15, RED = 8 * 32 * (32 * TN + 4) * 4;
-    constexpr size_t lds = (size_t)(8 * WREG > RED ? 8 * WREG : RED);
+    constexpr int NPIX = (PTH + KS - 1) * (PTW + KS - 1), WREG = (NPIX * PIXB + 15) & ~15, RED = NW * 32 * (32 * TN + 4) * 4;
+    constexpr size_t lds = (size_t)(NW * WREG > RED ? NW * WREG : RED);
     static_assert(lds <= 160 * 1024, "patch regions do not fit");
-    constexpr auto kern = k_conv_bf3_ks<PTH, PTW, TN, KS>;
+    static_assert(NW == 8 || lds <= 80 * 1024, "two four-wave workgroups share a CU's LDS");
+    constexpr auto kern = k_conv_bf3_ks<PTH, PTW, TN, KS, NW>;
     if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
     const int tiles_w = d.Wout / PTW, tiles_h = d.Hout / PTH;
     dim3 grid(tiles_w * tiles_h * nimg, (d.M + 31) / 32, 1);
-    IVLN_LAUNCH_FAMILY_NAMED("k_conv_bf3_ks", kern, grid, dim3(512), lds, s, d, a_split, (long long)grp_bytes, tiles_w, tiles_h, nimg);
+    IVLN_LAUNCH_FAMILY_NAMED("k_conv_bf3_ks", kern, grid, dim3(64 * NW), lds, s, d, a_split, (long long)grp_bytes, tiles_w, tiles_h, nimg);
+    ++g_bf3_ks_waves[NW == 8 ? 0 : 1];
     return IVLN_OK;
+}
+// (the 64-pixel tile of an 8- | 16- | 32-wide map with 8 or 4 waves)
+template <int KS>
+int launch_bf3_ks_px64(const ivln_gemm_desc& d, hipStream_t s, const unsigned char* a, int64_t gb, int nimg, bool nw4) {
+    if (d.Wout == 8) return nw4 ? launch_bf3_ks_tile<8, 8, 2, KS, 4>(d, s, a, gb, nimg) : launch_bf3_ks_tile<8, 8, 2, KS>(d, s, a, gb, nimg);
+    if (d.Wout == 16) return nw4 ? launch_bf3_ks_tile<4, 16, 2, KS, 4>(d, s, a, gb, nimg) : launch_bf3_ks_tile<4, 16, 2, KS>(d, s, a, gb, nimg);
+    return nw4 ? launch_bf3_ks_tile<2, 32, 2, KS, 4>(d, s, a, gb, nimg) : launch_bf3_ks_tile<2, 32, 2, KS>(d, s, a, gb, nimg);
+}
+
+// Four waves instead of eight (two co-resident workgroups per CU): where the eight-wave grid would run as two rounds - more
+// workgroups than CUs, at most twice as many - and every wave still gets two chunks.  nw_pin = 8 | 4 pins one (tile_override
+// 16 | 17 here, 18 | 19 for the 1x1 K-split form).  Kept per shape where it won: profiles/coresident_ks_sweep.txt.
+static bool bf3_ks_four_waves(int64_t wgs, int nch, int nw_pin) {
+    if (nw_pin) return nw_pin == 4;
+    const int64_t cus = ivln_cu_count();
+    return wgs > cus && wgs <= 2 * cus && nch >= 2 * 4;
 }
 
 // Eligibility of the K-split-over-waves kernel: deep 3x3 convs over few pixels.  mode: 0 = heuristic, 1 = insist (tests, tuning)
-int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_pin = 0) {
+int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_pin = 0, int nw_pin = 0) {
     if (d.Cin % CB != 0 || d.Cin < 8 * CB || d.stat_partials || d.splits > 1) return IVLN_E_UNSUPPORTED;
     if (d.bmode == BMODE_CONV_K2) {  // the stacked transposed-conv classes: 64-pixel tiles, no image groups
         if (d.grp_imgs > 0 || (d.Wout != 8 && d.Wout != 16 && d.Wout != 32) || d.Hout % (64 / d.Wout) != 0 || (d.in_img_stride & 3) ||
@@ -667,9 +704,7 @@ int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_p
         d.splits = 1;
         const unsigned char* a2 = (const unsigned char*)d.A_split;
         const int64_t gb2 = d.a_split_grp_stride * 4;
-        if (d.Wout == 8) return launch_bf3_ks_tile<8, 8, 2, 2>(d, s, a2, gb2, nimg);
-        if (d.Wout == 16) return launch_bf3_ks_tile<4, 16, 2, 2>(d, s, a2, gb2, nimg);
-        return launch_bf3_ks_tile<2, 32, 2, 2>(d, s, a2, gb2, nimg);
+        return launch_bf3_ks_px64<2>(d, s, a2, gb2, nimg, bf3_ks_four_waves(wgs2, d.Cin / CB, nw_pin));
     }
     if (d.Wout != 8 && d.Wout != 16 && d.Wout != 32) return IVLN_E_UNSUPPORTED;
     const int64_t wgs = (int64_t)(d.N / 64) * ((d.M + 31) / 32);
@@ -688,9 +723,7 @@ int bf3_ks_launch(ivln_gemm_desc& d, hipStream_t s, int nimg, int mode, int tn_p
         if (d.Wout == 16) return launch_bf3_ks_tile<2, 16, 1>(d, s, a, gb, nimg);
         return launch_bf3_ks_tile<1, 32, 1>(d, s, a, gb, nimg);
     }
-    if (d.Wout == 8) return launch_bf3_ks_tile<8, 8>(d, s, a, gb, nimg);
-    if (d.Wout == 16) return launch_bf3_ks_tile<4, 16>(d, s, a, gb, nimg);
-    return launch_bf3_ks_tile<2, 32>(d, s, a, gb, nimg);
+    return launch_bf3_ks_px64<3>(d, s, a, gb, nimg, bf3_ks_four_waves(wgs, d.Cin / CB, nw_pin));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -896,9 +929,11 @@ int bf3_conv7_pool_launch(ivln_gemm_desc& d, hipStream_t s) {
 // WT (wave tiles, short K: 64 ... 256 input channels - the bottleneck expansions 64 -> 256 ... 256 -> 1024 with their residual):
 // no K split at all - each of the workgroup's 4 waves owns its own 32 x 128 tile over the whole K and finishes it alone
 // (wave-private LDS for the transposing epilogue, no barrier anywhere); these launches are bound by their activation bytes.
-template <bool WT>
-__global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln_gemm_desc p, const unsigned char* a_split, long long a_grp_bytes) {
-    constexpr int NW = WT ? 4 : 8, TN = 4, DA = 4, BN = 128;
+// K-split form with NW = 4: two co-resident workgroups per CU for the grids that would run as two rounds (see k_conv_bf3_ks).
+template <bool WT, int NW = WT ? 4 : 8>
+__global__ __launch_bounds__(64 * NW, 2) void k_conv1x1_bf3_ks(const ivln_gemm_desc p, const unsigned char* a_split, long long a_grp_bytes) {
+    constexpr int TN = 4, DA = 4, BN = 128, BS = 64 * NW;
+    static_assert(WT ? NW == 4 : (NW == 8 || NW == 4), "wave tiles: 4 waves; K split: 8 or 4");
     constexpr int LDT = BN + 4;
     constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1104,8 +1139,8 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
         bf3_red_put<LDT>(red, wave, half, l31, acc);
         __syncthreads();
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int item = t + it * 512, r = item >> 6, j = item & 63;  // 16 (channel, a) x 64 pixel pairs
+        for (int it = 0; it < 16 * 64 / BS; ++it) {
+            const int item = t + it * BS, r = item >> 6, j = item & 63;  // 16 (channel, a) x 64 pixel pairs
             const int ml = 2 * r, nl = 2 * j, n = n0 + nl;
             const int e0 = nl & 3, q = nl >> 2;  // tile e, column q holds pixel 4 q + e
             const float* const r0 = red + ml * LDT + q + e0 * 32;  // rows ml and ml + 1, tiles e0 and e0 + 1
@@ -1121,14 +1156,14 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
         }
     } else {
     // (not bf3_quad_store: the operands are requested BEFORE the barrier, and the absent residual stays a branch - see the -0 remark)
-    constexpr int ITEMS = 2;  // 32 channels x 32 pixel quads = 1024 items over the workgroup's 512 threads
+    constexpr int ITEMS = 32 * 32 / BS;  // 32 channels x 32 pixel quads = 1024 items over the workgroup's 512 | 256 threads
     v4i rres[ITEMS];
     float esc[ITEMS], esh[ITEMS];
     int eoff[ITEMS];  // element offset of the item's quad in D / residual (< 2^29: checked by the launcher), -1 = outside
     const __amdgpu_buffer_rsrc_t rR = bf3_rsrc(p.residual), rS = bf3_rsrc(p.scale), rH = bf3_rsrc(p.shift);
     const bool has_res = p.residual != nullptr, has_sc = p.scale != nullptr, has_sh = p.shift != nullptr;
     auto request = [&](int it) {
-        const int item = t + it * 512, ml = item >> 5, q = item & 31;
+        const int item = t + it * BS, ml = item >> 5, q = item & 31;
         const int m = m0 + ml, n = n0 + 4 * q;
         const bool ok = m < p.M && n < p.N;
         const int img = n / HW, pp = n - img * HW;
@@ -1146,7 +1181,7 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
-        const int item = t + it * 512, ml = item >> 5, q = item & 31;
+        const int item = t + it * BS, ml = item >> 5, q = item & 31;
         float4 v = bf3_red_sum<NW, LDT, float4, 32>(red + ml * LDT + q);  // tile e, column q = pixel 4 q + e
         if (eoff[it] >= 0) {
             const int64_t addr = eoff[it];
@@ -1188,7 +1223,7 @@ __global__ __launch_bounds__(WT ? 256 : 512, 2) void k_conv1x1_bf3_ks(const ivln
 
 // Eligibility of the 1x1 kernels in their two forms.  mode: 0 = heuristic, 1 = insist; *kind: the form launched, as
 // ivln_conv_split_kinds counts it (2 = K split over the waves, 3 = wave tiles)
-int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin, int* kind) {
+int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin, int* kind, int nw_pin = 0) {
     if (d.stride != 1 || d.pad != 0 || d.Cin % CB != 0 || d.Cin < 4 * CB || d.stat_partials || d.splits > 1) return IVLN_E_UNSUPPORTED;
     if ((d.HoWo & 3) || (d.in_img_stride & 3) || ((((uintptr_t)d.B) | ((uintptr_t)d.D) | ((uintptr_t)d.residual)) & 15)) return IVLN_E_UNSUPPORTED;
     const int64_t nimg = d.N / d.HoWo;
@@ -1228,11 +1263,20 @@ int bf3_1x1_ks_launch(ivln_gemm_desc& d, hipStream_t s, int mode, int form_pin, 
         constexpr size_t lds = 0;  // (the wave-tile form keeps everything in registers)
         dim3 grid((unsigned)mtiles, (unsigned)((d.N + 511) / 512), 1);
         IVLN_LAUNCH_FAMILY(k_conv1x1_bf3_ks<true>, grid, dim3(256), lds, s, d, a, gb);
+    } else if (bf3_ks_four_waves(wgs, nch, nw_pin)) {  // two co-resident four-wave workgroups per CU
+        constexpr size_t lds = (size_t)4 * 32 * (128 + 4) * 4;
+        static_assert(lds <= 80 * 1024, "two four-wave workgroups share a CU's LDS");
+        constexpr auto kern = k_conv1x1_bf3_ks<false, 4>;
+        if (bf3_set_lds<kern>(lds) != IVLN_OK) return IVLN_E_HIP;
+        dim3 grid((unsigned)mtiles, (unsigned)((d.N + 127) / 128), 1);
+        IVLN_LAUNCH_FAMILY_NAMED("k_conv1x1_bf3_ks<false>", kern, grid, dim3(256), lds, s, d, a, gb);
+        ++g_bf3_ks_waves[3];
     } else {
         constexpr size_t lds = (size_t)8 * 32 * (128 + 4) * 4;
         if (bf3_set_lds<k_conv1x1_bf3_ks<false>>(lds) != IVLN_OK) return IVLN_E_HIP;
         dim3 grid((unsigned)mtiles, (unsigned)((d.N + 127) / 128), 1);
         IVLN_LAUNCH_FAMILY(k_conv1x1_bf3_ks<false>, grid, dim3(512), lds, s, d, a, gb);
+        ++g_bf3_ks_waves[2];
     }
     return IVLN_OK;
 }
@@ -1872,6 +1916,14 @@ extern "C" int ivln_conv_split_kinds(long long* out4, int reset) {
     if (reset) for (int i = 0; i < 4; ++i) g_bf3_kind[i] = 0;
     return IVLN_OK;
 }
+/* launches of the K-split kernels by wave count since the last reset: [0] k_conv_bf3_ks with 8 waves, [1] with 4,
+ * [2] k_conv1x1_bf3_ks' K-split form with 8 waves, [3] with 4 ([0] + [1] and [2] are launches ivln_conv_split_kinds counts
+ * under [1] and [2]; the pooled map-CNN kernel, also under its [1], is not counted here) */
+extern "C" int ivln_conv_ks_waves(long long* out4, int reset) {
+    if (out4) for (int i = 0; i < 4; ++i) out4[i] = g_bf3_ks_waves[i];
+    if (reset) for (int i = 0; i < 4; ++i) g_bf3_ks_waves[i] = 0;
+    return IVLN_OK;
+}
 
 #ifdef BF3_TIMING
 extern "C" int ivln_conv_bf3_stamps(unsigned long long* host, int n) {
@@ -1912,7 +1964,8 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
             return IVLN_E_UNSUPPORTED;
         const int ovu = d.tile_override;
         int kind1 = 2;  // (the form the launcher took: a pinned form or 24 / 32 / 48 chunks over many pixels is not the chunk count's)
-        const int rc = bf3_1x1_ks_launch(d, s, (force || ovu == 11 || ovu == 12 || ovu == 13) ? 1 : 0, ovu == 12 ? 0 : (ovu == 13 ? 1 : -1), &kind1);
+        const int nwu = ovu == 18 ? 8 : (ovu == 19 ? 4 : 0);  // (18 | 19: the K-split form with 8 | 4 waves)
+        const int rc = bf3_1x1_ks_launch(d, s, (force || ovu == 11 || ovu == 12 || ovu == 13 || nwu) ? 1 : 0, (ovu == 12 || nwu) ? 0 : (ovu == 13 ? 1 : -1), &kind1, nwu);
         return done(rc, flops, kind1, -1);
     }
     if (KS == 2) {
@@ -1928,8 +1981,10 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
         if (convt_off && !force) return IVLN_E_UNSUPPORTED;
         const int ov2 = d.tile_override;
         if (ov2 < 20) {  // few pixels: K split over the waves
-            const int rc = bf3_ks_launch(d, s, nimg2, (ov2 == 10 || ov2 == 15) ? 1 : 0);
-            if (rc != IVLN_E_UNSUPPORTED || ov2 == 10 || ov2 == 15) return done(rc, flops2, 1, -1);
+            const int nw2 = ov2 == 16 ? 8 : (ov2 == 17 ? 4 : 0);  // (16 | 17: 8 | 4 waves)
+            const bool ins2 = ov2 == 10 || ov2 == 15 || nw2;
+            const int rc = bf3_ks_launch(d, s, nimg2, ins2 ? 1 : 0, 0, nw2);
+            if (rc != IVLN_E_UNSUPPORTED || ins2) return done(rc, flops2, 1, -1);
         }
         const int CUS2 = ivln_cu_count();
         auto blocks2 = [&](int cfg) {
@@ -1948,14 +2003,16 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     // IVLN_BF3_1X1_KS=0 | 1 = never | wherever eligible, tile_override 11 insists
     static const int ks1_env = getenv("IVLN_BF3_1X1_KS") ? atoi(getenv("IVLN_BF3_1X1_KS")) : -1;
     // (tuning, tools/conv_cfg_sweep.py: tile_override 12 / 13 insist on the K-split / wave-tile form, 14 / 15 on 32- / 64-pixel tiles
-    //  of the 3x3 K-split kernel, 20 + c on tile c of the tiled kernel)
+    //  of the 3x3 K-split kernel, 16 / 17 on its 64-pixel tiles with 8 / 4 waves - the stacked 2 x 2 form too -, 18 / 19 on the 1x1
+    //  K-split form with 8 / 4 waves, 20 + c on tile c of the tiled kernel; without a pin the wave count is bf3_ks_four_waves')
     const int ov = d.tile_override;
     const bool post = d.residual_after_relu != 0;  // (only the stride-1 1x1 kernels below know this epilogue form: they are insisted on)
-    const bool ins1 = ov == 11 || ov == 12 || ov == 13 || post, ins3 = ov == 10 || ov == 14 || ov == 15;
+    const int nw3 = ov == 16 ? 8 : (ov == 17 ? 4 : 0), nw1 = ov == 18 ? 8 : (ov == 19 ? 4 : 0);
+    const bool ins1 = ov == 11 || ov == 12 || ov == 13 || nw1 || post, ins3 = ov == 10 || ov == 14 || ov == 15 || nw3;
     if (KS == 1 && ov < 20 && (ks1_env != 0 || ins1) && d.splits <= 1 && !d.defer_epilogue && d.HoWo == d.Hout * d.Wout &&
         d.K == d.Cin && d.N % d.HoWo == 0 && d.Hout == d.Hin && d.Wout == d.Win) {
         int kind1 = 2;
-        const int rc = bf3_1x1_ks_launch(d, s, (ks1_env == 1 || ins1) ? 1 : 0, ov == 12 ? 0 : (ov == 13 ? 1 : -1), &kind1);
+        const int rc = bf3_1x1_ks_launch(d, s, (ks1_env == 1 || ins1) ? 1 : 0, (ov == 12 || nw1) ? 0 : (ov == 13 ? 1 : -1), &kind1, nw1);
         if (rc != IVLN_E_UNSUPPORTED || ins1) return done(rc, flops, kind1, 0);
     }
     if (ins1 || (ins3 && KS != 3)) return IVLN_E_UNSUPPORTED;
@@ -1997,7 +2054,7 @@ int ivln_conv_bf3_launch(ivln_gemm_desc& d, hipStream_t s, bool force) {
     // pixel-starved deep 3x3 convs: K split over the waves of a workgroup, no slabs (k_conv_bf3_ks); IVLN_BF3_KS=0 | 1 = never | wherever eligible
     static const int ks_env = getenv("IVLN_BF3_KS") ? atoi(getenv("IVLN_BF3_KS")) : -1;
     if (KS == 3 && !s2 && ov < 20 && (ks_env != 0 || ins3) && d.splits <= 1) {
-        const int rc = bf3_ks_launch(d, s, nimg, (ks_env == 1 || ins3) ? 1 : 0, ov == 14 ? 1 : (ov == 15 ? 2 : 0));
+        const int rc = bf3_ks_launch(d, s, nimg, (ks_env == 1 || ins3) ? 1 : 0, ov == 14 ? 1 : ((ov == 15 || nw3) ? 2 : 0), nw3);
         if (rc != IVLN_E_UNSUPPORTED || ins3) return done(rc, flops, 1, 0);
     }
     const int nch = ((d.Cin + CB - 1) / CB + bf3_stage_chunks(KS) - 1) / bf3_stage_chunks(KS);  // stages: what blockIdx.z can split
