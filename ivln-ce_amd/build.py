@@ -34,6 +34,8 @@ SOURCES = {
     "seg_loss.hip": [],
     # (the augmentation's float steps round where they are written, as its float32 restatement in the tests does)
     "seg_augment.hip": ["-ffp-contract=off"],
+    # (the renderer's float steps round where they are written: boxworld.render_reference equals it bit for bit)
+    "boxworld.hip": ["-ffp-contract=off"],
     "dtw.cpp": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -64,6 +66,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_tour_state.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_depth_backbones.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_conv_ks_waves.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_boxworld.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

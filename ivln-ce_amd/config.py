@@ -181,7 +181,16 @@ def _experiment_defaults() -> Config:
     _C.CMD_TRAILING_OPTS = []
     _C.TRAINER_NAME = "dagger"
     _C.ENV_NAME = "VLNCEDaggerEnv"
-    _C.ENV_BACKEND = "synthetic"  # envs.construct_envs: the only vector env this package's trainers drive
+    _C.ENV_BACKEND = "synthetic"  # envs.construct_envs: "synthetic" (noise frames) or "boxworld" (frames ray-cast from the pose)
+    # --- the box-world backend (boxworld.make_scene; not a reference key) ---
+    _C.BOXWORLD = CN()
+    _C.BOXWORLD.ROOM_SIZE = [8.0, 2.5, 10.0]     # x, y (height), z in metres
+    _C.BOXWORLD.ROOM_JITTER = 0.1                # x and z are scaled by 1 +- this, per scene
+    _C.BOXWORLD.ROOM_ORIGIN_Z = 0.4              # the scene origin lies this share of the depth from the +z wall
+    _C.BOXWORLD.NUM_BOXES = 12                   # drawn per scene (at most 32); boxes over an episode start are left out
+    _C.BOXWORLD.BOX_MIN_SIZE = [0.4, 0.4, 0.4]
+    _C.BOXWORLD.BOX_MAX_SIZE = [1.5, 2.0, 1.5]
+    _C.BOXWORLD.START_CLEARANCE = 0.5            # metres kept free around every episode start
     _C.SIMULATOR_GPU_IDS = [0]
     _C.VIDEO_OPTION = []
     _C.VIDEO_DIR = "data/videos/debug"

@@ -20,6 +20,10 @@ Habitat-Sim, MP3D and R2R-CE do not exist on the GPU box (simulator side is out 
 8-9): this stand-in feeds the hot path observations of exactly the sensor dtypes/shapes of section 8a row A0, a
 scripted expert (`shortest_path_sensor`) and a kinematic agent in obstacle-free space (0.25 m forward / 15 degree
 turns; the oracle is a turn-then-advance follower), so positions, tours and t-nDTW are meaningful.
+
+`BoxWorldVectorEnv` (ENV_BACKEND "boxworld") is the same env in a consistent 3-D world: each env lives in a room with
+boxes, its depth / semantic12 / rgb are ray-cast from the pose by the mapper's camera model - on the device, where the
+mapper and RedNet read them (boxworld.py, csrc/boxworld.hip) - and the agent collides with walls and boxes.
 """
 import math
 from types import SimpleNamespace
@@ -318,6 +322,8 @@ class _SynthEnv:
 
 
 class SyntheticVectorEnv:
+    _ENV = _SynthEnv  # the per-env class (BoxWorldVectorEnv: _BoxEnv)
+
     def __init__(self, config, num_envs=None, seed=None, rank=0, world=1, iterative=None, auto_reset_done=True,
                  **env_kw):
         n = num_envs if num_envs is not None else config.NUM_ENVIRONMENTS
@@ -331,7 +337,7 @@ class SyntheticVectorEnv:
         needs_rgb = (config.MODEL.policy_name == "LatentCMAPolicy"
                      or any("Predicted" in t for t in config.RL.POLICY.OBS_TRANSFORMS.ENABLED_TRANSFORMS))
         env_kw.setdefault("with_rgb", needs_rgb)
-        self._envs: List[_SynthEnv] = [_SynthEnv(i, seed + 1000 * i, config, iterative=self.iterative, **env_kw)
+        self._envs: List[_SynthEnv] = [self._ENV(i, seed + 1000 * i, config, iterative=self.iterative, **env_kw)
                                        for i in ids]
         self._paused: List[_SynthEnv] = []
         d = config.TASK_CONFIG.SIMULATOR.DEPTH_SENSOR
@@ -400,21 +406,226 @@ class SyntheticVectorEnv:
         self._envs, self._paused = [], []
 
 
+class _BoxEnv(_SynthEnv):
+    """`_SynthEnv` in a box-world scene (boxworld.make_scene): the episodes, scripts and tokens are drawn exactly as the
+    parent draws them, then every script is simulated against the scene and a FORWARD that would be blocked is replaced
+    by a LEFT turn, so the scripted expert and `expert_path` are collision-free.  The agent is a disc of
+    SIMULATOR.AGENT_0.RADIUS: a FORWARD that would leave the room or enter a box footprint grown by the radius leaves the
+    pose unchanged.  A blocked oracle step uses up the oracle's error budget at once (`_oracle_action_safe` gives up,
+    teleporting where the parent would): the turn-then-advance follower has no way round a box.  The frames are not made
+    here: the vector env renders all its envs in one call and fills them in."""
+
+    def __init__(self, idx, seed, cfg, **kw):
+        super().__init__(idx, seed, cfg, **kw)
+        from .boxworld import intrinsics, make_scene
+
+        sim = cfg.TASK_CONFIG.SIMULATOR
+        self.radius = float(sim.AGENT_0.RADIUS)
+        self.depth_cam = (math.radians(float(sim.DEPTH_SENSOR.HFOV)), float(sim.DEPTH_SENSOR.MIN_DEPTH),
+                          float(sim.DEPTH_SENSOR.MAX_DEPTH))
+        self.rgb_hfov = math.radians(float(sim.RGB_SENSOR.HFOV))
+        self.depth_f = intrinsics(self.H, self.W, self.depth_cam[0])
+        self.rgb_f = intrinsics(*self.rgb_hw, self.rgb_hfov)
+        self.scene_name = f"bw{idx}"
+        self.scene = make_scene(seed + 13, cfg, origin=(float(idx) * 3.0, 0.0, 0.0),
+                                starts=[ep.start for ep in self.episodes])
+        self.scene_index = -1  # its entry in the device renderer's table (BoxWorldVectorEnv)
+        self._oracle_blocked = False
+        for ep in self.episodes:
+            if self.scene.blocked(ep.start, self.radius):
+                raise ValueError(f"box-world scene {self.scene_name}: the start of episode {ep.episode_id} is not free "
+                                 "(BOXWORLD.ROOM_SIZE too small for the episode starts?)")
+            ep.scene_id = self.scene_name
+            pose, heading = ep.start.copy(), ep.start_heading
+            for t, a in enumerate(ep.script):
+                if a == FORWARD and self._forward_blocked(pose, heading):
+                    a = ep.script[t] = LEFT
+                heading = _advance(pose, heading, a)
+            ep.goal = np.array(self._gt_positions(ep)[-1], np.float32)
+
+    def _forward_blocked(self, pose, heading):
+        p = pose.copy()
+        _advance(p, heading, FORWARD)
+        return self.scene.blocked(p, self.radius)
+
+    def _move(self, a):
+        """One action under collision; False when a FORWARD was blocked (the pose is unchanged)."""
+        if a == FORWARD and self._forward_blocked(self.pose, self.heading):
+            return False
+        self.heading = _advance(self.pose, self.heading, a)
+        return True
+
+    def _obs(self):
+        ep = self.current_episode
+        expert = ep.script[self.t] if (self.phase == "agent" and self.t < len(ep.script)) else STOP
+        obs = {
+            "depth": None,  # (filled by the vector env's batched render, like semantic12 / rgb below)
+            "instruction": ep.tokens.copy(),
+            "world_robot_pose": self.pose.copy(),
+            "world_robot_orientation": np.array([0.0, self.heading], np.float64),
+            "env_name": ep.scene_id,
+            "progress": np.array([min(1.0, self.t / max(1, len(ep.script)))], np.float64),
+            "shortest_path_sensor": np.array([float(expert)], np.float64),
+        }
+        if self.text_features is not None:
+            del obs["instruction"]
+            obs["rxr_instruction"] = ep.features
+        if self.with_semantic:
+            obs["semantic12"] = None
+        if self.with_rgb:
+            obs["rgb"] = None
+        return obs
+
+    def render_host(self, obs):
+        """The CPU path: this env's frames from `boxworld.render_reference`, as numpy arrays."""
+        from .boxworld import render_reference
+
+        pose, heading = obs["world_robot_pose"], float(obs["world_robot_orientation"][1])
+        _, dmin, dmax = self.depth_cam
+        f = render_reference(self.scene, pose, heading, self.H, self.W, *self.depth_f, dmin, dmax, with_rgb=False)
+        obs["depth"] = f["depth"][..., None]
+        if self.with_semantic:
+            obs["semantic12"] = f["labels"][..., None]
+        if self.with_rgb:
+            obs["rgb"] = render_reference(self.scene, pose, heading, *self.rgb_hw, *self.rgb_f, dmin, dmax)["rgb"]
+
+    def _agent_step(self, action):
+        self._move(int(action))
+        self.t += 1
+        self._positions.append([float(x) for x in self.pose])
+        return int(action) == STOP or self.t >= min(self.max_steps, 4 * len(self.current_episode.script))
+
+    def _oracle_action_safe(self, position_to, heading_to, teleport_on_failure):
+        if self._oracle_blocked:  # the budget is spent: the parent's give-up branch
+            self._oracle_blocked = False
+            if teleport_on_failure:
+                self.pose = np.array(position_to, np.float32)
+                if heading_to is not None:
+                    self.heading = heading_to
+            return STOP
+        return super()._oracle_action_safe(position_to, heading_to, teleport_on_failure)
+
+    def _next_phase(self):
+        super()._next_phase()
+        self._oracle_blocked = False
+
+    def _step_oracle(self):
+        ep = self.current_episode
+        to, heading_to = (ep.goal, None) if self.phase == "oracle_goal" else (ep.start, ep.start_heading)
+        self._oracle_blocked = not self._move(self._oracle_action(to, heading_to))
+        nxt = self._oracle_action_safe(to, heading_to, self.phase == "oracle_start")
+        if nxt == STOP:
+            if self.phase == "oracle_start":
+                if self.precise_start:
+                    self.pose, self.heading = ep.start.copy(), ep.start_heading
+                self._positions = [[float(x) for x in self.pose]]
+            self._next_phase()
+        else:
+            self._oracle_steps += 1
+        return self._obs()
+
+
+class BoxWorldVectorEnv(SyntheticVectorEnv):
+    """`SyntheticVectorEnv` whose observations are a consistent 3-D world (ENV_BACKEND "boxworld"): env i lives in scene
+    `bw{i}` and its depth, semantic12 and rgb are ray-cast from its pose by the mapper's own camera model (boxworld.py).
+    Same step protocols, kwargs, observation keys, dtypes, shapes and spaces as the parent.  On a GPU all envs of a step
+    are rendered in ONE call (csrc/boxworld.hip) and the three frame entries of every observation are device-tensor views
+    of the batched buffers, valid through the next step - `utils.batch_obs` stacks them without a host round trip; on the
+    CPU they are numpy arrays from `boxworld.render_reference` (the same bits).  `device`: where to render ("cpu", a cuda
+    device; default: cuda:TORCH_GPU_ID when there is one)."""
+    _ENV = _BoxEnv
+
+    def __init__(self, config, *args, device=None, **kw):
+        import torch
+
+        super().__init__(config, *args, **kw)
+        if device is None:
+            device = torch.device("cuda", int(config.TORCH_GPU_ID)) if torch.cuda.is_available() else torch.device("cpu")
+        self.device = torch.device(device)
+        self._renderer = None
+        if self.device.type == "cuda" and self._envs:
+            from .boxworld import BoxWorldRenderer
+
+            e0 = self._envs[0]
+            hfov, dmin, dmax = e0.depth_cam
+            self._renderer = BoxWorldRenderer(self.device, len(self._envs), (e0.H, e0.W), hfov, dmin, dmax,
+                                              rgb_hw=e0.rgb_hw if e0.with_rgb else None, rgb_hfov_rad=e0.rgb_hfov)
+            for e in self._envs:
+                e.scene_index = self._renderer.add_scene(e.scene)
+
+    def _fill(self, observations):
+        """The frames of every env's observation: one render call on a GPU."""
+        envs = self._envs
+        if self._renderer is None:
+            for e, o in zip(envs, observations):
+                e.render_host(o)
+            return
+        fr = self._renderer.render([e.scene_index for e in envs], [o["world_robot_pose"] for o in observations],
+                                   [o["world_robot_orientation"][1] for o in observations], with_rgb=envs[0].with_rgb)
+        for b, (e, o) in enumerate(zip(envs, observations)):
+            self._assign(e, o, {k: v[b] for k, v in fr.items()})
+
+    @staticmethod
+    def _assign(e, o, fr):
+        o["depth"] = fr["depth"]
+        if e.with_semantic:
+            o["semantic12"] = fr["labels"]
+        if e.with_rgb:
+            o["rgb"] = fr["rgb"]
+
+    def reset(self):
+        out = super().reset()
+        if out:
+            self._fill([x[0] for x in out] if self.iterative else out)
+        return out
+
+    def step(self, actions):
+        out = super().step(actions)
+        if out:
+            self._fill([x[0] for x in out])
+        return out
+
+    def reset_at(self, i):
+        out = super().reset_at(i)
+        e, o = self._envs[i], (out[0][0] if self.iterative else out[0])
+        if self._renderer is None:
+            e.render_host(o)
+        else:  # row i's own buffers: the other envs' views of the last step stay what they are
+            self._assign(e, o, self._renderer.render_row(i, e.scene_index, o["world_robot_pose"],
+                                                         o["world_robot_orientation"][1], with_rgb=e.with_rgb))
+        return out
+
+    def scenes(self):
+        """{scene name: boxworld.Scene} of every env, paused ones included."""
+        return {e.scene_name: e.scene for e in self._envs + self._paused}
+
+    def check_status(self):
+        if self._renderer is not None:
+            self._renderer.check_status()
+
+    def close(self):
+        super().close()
+        self._renderer = None
+
+
 def construct_envs(config, env_class=None, auto_reset_done=True, rank=0, world=1, **kw):
     """The vector env the trainers of this package drive (the reference: env_utils.py:25-114; `auto_reset_done`
     False = `construct_envs_auto_reset_false`).  The step protocol follows `config.ENV_NAME` ("Iterative" in the
     name -> the 7-tuple protocol) unless `iterative=` says otherwise.
 
-    Only the synthetic backend exists in this scope (simulator side: SURVEY.md section 2 rows 8-9).  The choice is
-    explicit: `config.ENV_BACKEND` ("synthetic", the default of this package's config) or the IVLN_ENV_BACKEND
-    environment variable; anything else fails loudly instead of silently training on synthetic observations.  The
-    trainers themselves speak the reference's env protocol, so a Habitat `ExtendedVectorEnv` can be handed to
-    them where Habitat exists."""
+    Two backends exist in this scope (simulator side: SURVEY.md section 2 rows 8-9), neither of them Habitat: "synthetic"
+    (`SyntheticVectorEnv`: frames are noise, the default of this package's config) and "boxworld" (`BoxWorldVectorEnv`:
+    frames ray-cast from the pose in a room with boxes, on the device).  The choice is explicit: `config.ENV_BACKEND` or
+    the IVLN_ENV_BACKEND environment variable; anything else fails loudly instead of silently training on synthetic
+    observations.  The trainers themselves speak the reference's env protocol, so a Habitat `ExtendedVectorEnv` can be
+    handed to them where Habitat exists."""
     import os
 
     backend = os.environ.get("IVLN_ENV_BACKEND") or str(getattr(config, "ENV_BACKEND", "synthetic"))
+    if backend == "boxworld":
+        return BoxWorldVectorEnv(config, rank=rank, world=world, auto_reset_done=auto_reset_done, **kw)
     if backend != "synthetic":
         raise NotImplementedError(
-            f"ENV_BACKEND={backend!r}: ivln_ce_amd.envs only builds the synthetic vector env; real Habitat envs "
-            "come from the reference's construct_envs (same step protocol)")
+            f"ENV_BACKEND={backend!r}: ivln_ce_amd.envs builds the synthetic and the boxworld vector envs only; real "
+            "Habitat envs come from the reference's construct_envs (same step protocol)")
     return SyntheticVectorEnv(config, rank=rank, world=world, auto_reset_done=auto_reset_done, **kw)

@@ -1095,6 +1095,17 @@ class _PolicyStepper:
         return actions, rnn_states
 
 
+def _host_record(o):
+    """A stored step outlives the env's frame buffers: the box-world backend hands out device views that stay valid for one
+    more step only, so whatever device tensor is left in a record (frames the policy's feature caches did not replace) is
+    copied to the host here.  Numpy observations (the synthetic backend) pass through untouched."""
+    for k in ("depth", "semantic12", "rgb"):
+        v = o.get(k)
+        if torch.is_tensor(v) and v.is_cuda:
+            o[k] = v.cpu()
+    return o
+
+
 class _RolloutStepper(_PolicyStepper):
     """One sampled, expert-mixed policy step of a DAgger collection loop (dagger_trainer.py:416-427, 469-472;
     iterative_collection_dagger_trainer.py:300-348) and the per-step host copies the loops store, on `_PolicyStepper`'s
@@ -1352,7 +1363,7 @@ class DaggerTrainer(BaseVLNCETrainer):
                         o["occupancy_map"], o["semantic_map"] = host["occ"][i], host["sem"][i]
                         for k in MAP_SOURCE_KEYS + ("rgb",):
                             o.pop(k, None)
-                    episodes[i].append((o, prev_host[i], experts[i], tours_now[i]))
+                    episodes[i].append((_host_record(o), prev_host[i], experts[i], tours_now[i]))
                 skips = [int(e) == -1 for e in experts]
                 prev_actions = actions
                 prev_host = host["actions"]
@@ -1552,7 +1563,8 @@ class IterativeCollectionDaggerTrainer(DaggerTrainer):
                     if "rgb" in observations[i]:
                         del observations[i]["rgb"]
                     observations[i].pop("episode_not_done_masks", None)  # (the captured step's extra mask key)
-                    episodes[i].append((observations[i], prev_host[i], expert_host[i], current_episode.tour_id))
+                    episodes[i].append((_host_record(observations[i]), prev_host[i], expert_host[i],
+                                        current_episode.tour_id))
                 skips = [int(e) == -1 for e in expert_host]
                 prev_actions = actions
                 prev_host = host["actions"]

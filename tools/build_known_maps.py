@@ -7,9 +7,11 @@ reads from data/known_maps/predicted_semantics.
     python tools/build_known_maps.py [--exp-config <yaml>] --out data/known_maps/gt_semantics --steps-per-scene 200 [--predicted]
                                      [KEY VALUE ...]   (trailing config overrides)
 
-The vector env is the synthetic backend today (ivln_ce_amd.envs.construct_envs): env i stays in scene{i}, an episode that
-ends is followed by the next one of the same scene and the scene's cloud keeps growing across that boundary.  Prints one
-JSON line {scene: points}."""
+The vector env comes from ivln_ce_amd.envs.construct_envs, so the backend is chosen through the trailing overrides:
+`ENV_BACKEND synthetic` (the default: env i stays in scene{i}, its frames are noise) or `ENV_BACKEND boxworld` (env i stays
+in the room bw{i}; depth and labels are ray-cast from the pose on the device, so the files hold the room's surfaces: every
+point of label L lies on a box of label L, `boxworld.surface_distance`).  An episode that ends is followed by the next one
+of the same scene and the scene's cloud keeps growing across that boundary.  Prints one JSON line {scene: points}."""
 import argparse
 import json
 import os

@@ -14,6 +14,9 @@ first --weight-batches batches of the stream, which are then trained on like the
 taken from the stream before training and never trained on; every --eval-every steps (0: never) and at the end one line
 {step, holdout_miou, holdout_pixel_acc}.
 
+The observation stream is the backend's (trailing `ENV_BACKEND boxworld`: rgb, depth and labels of one consistent world,
+rendered on the device; the default synthetic backend draws labels that are independent of the image).
+
 Prints one JSON line per 10 steps {step, loss, per_scale} and a last one with the mIoU of the final batch."""
 import argparse
 import itertools
