@@ -40,7 +40,9 @@ typedef struct ivln_mapper ivln_mapper;
 int ivln_mapper_create(int B_max, int H, int W, double vfov_rad, double height_m, double width_m,
                        double res_m, int64_t world_capacity, int64_t table_cells, ivln_mapper** out);
 int ivln_mapper_destroy(ivln_mapper* m);
-/* Forget the world cloud (new process / new eval). */
+/* Forget the world cloud (new process / new eval).  Closes the mapper (see ivln_mapper_step_begin) and leaves the
+ * keep-highest table all zero - on every reset, not only when a _begin is open: one asynchronous memset on `stream`.
+ * What an unfinished _begin or a step that raised IVLN_E_* left behind is gone afterwards. */
 int ivln_mapper_reset(ivln_mapper* m, void* stream);
 
 /* Launch width of the step's kernels: the local-cloud kernels on `local_blocks` workgroups; the world-cloud kernels on
@@ -78,7 +80,15 @@ int ivln_mapper_step_posed(ivln_mapper* m, const float* depth, const uint8_t* la
  * enqueued on another stream than _finish as long as _finish is ordered behind it.  _finish takes the T / rot that _begin
  * wrote (T_out, rot_out) and the same depth, pose, not_done and B; nothing on the host links the two calls (a captured step
  * records each half once and replays them many times), so a _finish without its _begin is the caller's error: it would
- * select from the previous step's arg-max table. */
+ * select from the previous step's arg-max table.
+ * Open state.  The table is all zero between complete steps: only the winner of a slot clears it, in _finish.  A _begin
+ * therefore OPENS the mapper - a host-side flag of the handle, moved by calls and not by launches: a captured replay does
+ * not move it and need not -, a _finish or ivln_mapper_reset closes it.  While it is open the entries of the unfinished
+ * arg-max sit in the table, and every call that would meet them returns IVLN_E_INVALID, launches nothing and writes
+ * nothing: a second _begin, ivln_mapper_step / _step_posed, ivln_mapper_env_export, ivln_known_lib_add_from_mapper,
+ * ivln_mapper_env_append / _append_from_lib and ivln_mapper_rows_clear.  A _begin that is never finished is undone by
+ * ivln_mapper_reset alone.  A _finish on a closed mapper stays accepted (a split capture records it once per phase for a
+ * single _begin). */
 int ivln_mapper_step_begin(ivln_mapper* m, const float* depth, const float* pose, const double* orientation,
                            const uint8_t* not_done, int B, uint8_t* occ_out, float* T_out, float* rot_out, void* stream);
 int ivln_mapper_step_finish(ivln_mapper* m, const float* depth, const uint8_t* labels, const float* T, const float* pose,

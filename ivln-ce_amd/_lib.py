@@ -56,6 +56,8 @@ def _sig(L):
     L.ivln_mapper_rows_clear.argtypes = [vp, vp, i32, vp]
     L.ivln_mapper_env_append.argtypes = [vp, i32, vp, vp, i64, vp]
     L.ivln_mapper_env_append_from_lib.argtypes = [vp, i32, vp, i32, vp]
+    # include/ivln_mapper_debug.h (tests only)
+    L.ivln_mapper_debug_nonzero.argtypes = [vp, C.POINTER(i64), vp]
 
 
 def lib():

@@ -67,6 +67,7 @@ def build_all(force=False, verbose=True):
     headers.append(os.path.join(HERE, "..", "include", "ivln_depth_backbones.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_conv_ks_waves.h"))
     headers.append(os.path.join(HERE, "..", "include", "ivln_boxworld.h"))
+    headers.append(os.path.join(HERE, "..", "include", "ivln_mapper_debug.h"))
     procs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

@@ -28,6 +28,7 @@
 #include "../../include/ivln_known_lib.h"
 #include "../../include/ivln_map_build.h"
 #include "../../include/ivln_map_seed.h"
+#include "../../include/ivln_mapper_debug.h"
 
 namespace {
 
@@ -951,6 +952,17 @@ __global__ __launch_bounds__(kThreads) void k_env_append(const float* __restrict
     }
 }
 
+// ---- the arg-max table's invariant, observed (include/ivln_mapper_debug.h): non-zero words of a buffer.  Plain loads, a
+// wave reduction, one atomicAdd per wave that found any. ----
+__global__ __launch_bounds__(kThreads) void k_debug_nonzero(const unsigned long long* __restrict__ p, int64_t n,
+                                                            unsigned long long* __restrict__ count) {
+    unsigned long long c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) c += p[i] != 0ull;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
 }  // namespace
 
 struct ivln_known_lib {
@@ -986,6 +998,10 @@ struct ivln_mapper {
     unsigned* env_part;       // device: per-block, per-env {count, lowest rank, highest rank} of k_env_stats
     unsigned* env_part_host;  // host copy the blocks are folded from
     unsigned* scan_buf;       // device: the scan's levels above the marks, level 1 first
+    // host-side: an ivln_mapper_step_begin whose _finish has not been issued - its arg-max entries sit in tab64 and every call
+    // that reads the table or the cloud is refused (include/ivln_hip.h).  Set by calls, not by launches: a captured replay
+    // does not move it.
+    bool open;
 };
 
 #define HIPCHK(x)                          \
@@ -1043,6 +1059,7 @@ int ivln_mapper_create(int B_max, int H, int W, double vfov_rad, double height_m
     if (m->table_cells > (1ll << 31)) m->table_cells = 1ll << 31;  // ranks = keys must fit 31 bits (k_world_max)
     m->known_rank = 0;
     m->seed_rank = 0;
+    m->open = false;
     m->klib = nullptr; m->kcur = nullptr; m->krot = nullptr; m->kcount = nullptr;
     m->env_part = nullptr; m->env_part_host = nullptr; m->scan_buf = nullptr;
     m->local_blocks = m->world_blocks = 0;
@@ -1113,6 +1130,10 @@ int ivln_mapper_reset(ivln_mapper* m, void* stream) {
     if (!m) return IVLN_E_INVALID;
     m->known_rank = 0;
     m->seed_rank = 0;
+    // whatever an unfinished ivln_mapper_step_begin (or a step that raised IVLN_E_*) left in the arg-max table goes with the
+    // cloud: the next step's winners must find their own entries there, not a forgotten frame's
+    HIPCHK(hipMemsetAsync(m->tab64, 0, sizeof(unsigned long long) * (size_t)m->table_cells, (hipStream_t)stream));
+    m->open = false;
     if (m->kcur) HIPCHK(hipMemsetAsync(m->kcur, 0xFF, sizeof(int) * (size_t)m->B_max, (hipStream_t)stream));  // -1: no scene
     return init_scalars(m, (hipStream_t)stream);
 }
@@ -1153,7 +1174,8 @@ static int mapper_begin(ivln_mapper* m, const float* depth, const float* T, cons
 
 // The rest of the step begun by mapper_begin (same batch, same T / pose / rot, same launch width): label the surviving local
 // points, merge them into the world cloud, raster.  No host-side state links the two halves - a captured step records each
-// half once and replays them many times -, the kernels' own state (arg-max table, block partials) does.
+// half once and replays them many times -, the kernels' own state (arg-max table, block partials) does.  (The handle's
+// `open` flag links nothing: it only refuses the calls that must not meet an unfinished arg-max in the table.)
 static int mapper_finish(ivln_mapper* m, const float* depth, const uint8_t* labels, const float* T, const float* pose,
                          const float* rot, const uint8_t* not_done, int B, uint8_t* occ_out, uint8_t* sem_out, void* stream) {
     if (!m || B <= 0 || B > m->B_max) return IVLN_E_INVALID;
@@ -1192,26 +1214,32 @@ static int mapper_step(ivln_mapper* m, const float* depth, const uint8_t* labels
 int ivln_mapper_step_begin(ivln_mapper* m, const float* depth, const float* pose, const double* orientation,
                            const uint8_t* not_done, int B, uint8_t* occ_out, float* T_out, float* rot_out, void* stream) {
     if (!depth || !pose || !orientation || !T_out || !rot_out || !not_done || !occ_out) return IVLN_E_INVALID;
-    return mapper_begin(m, depth, nullptr, pose, nullptr, orientation, T_out, rot_out, not_done, B, occ_out, stream);
+    if (m && m->open) return IVLN_E_INVALID;  // (a second arg-max on top of the first one's entries)
+    const int rc = mapper_begin(m, depth, nullptr, pose, nullptr, orientation, T_out, rot_out, not_done, B, occ_out, stream);
+    if (rc == IVLN_OK) m->open = true;
+    return rc;
 }
 
 int ivln_mapper_step_finish(ivln_mapper* m, const float* depth, const uint8_t* labels, const float* T, const float* pose,
                             const float* rot, const uint8_t* not_done, int B, uint8_t* occ_out, uint8_t* sem_out, void* stream) {
     if (!depth || !labels || !T || !pose || !rot || !not_done || !occ_out || !sem_out) return IVLN_E_INVALID;
-    return mapper_finish(m, depth, labels, T, pose, rot, not_done, B, occ_out, sem_out, stream);
+    // (accepted on a closed mapper as well: a split capture records _finish once per phase behind a single _begin)
+    const int rc = mapper_finish(m, depth, labels, T, pose, rot, not_done, B, occ_out, sem_out, stream);
+    if (rc == IVLN_OK) m->open = false;
+    return rc;
 }
 
 int ivln_mapper_step(ivln_mapper* m, const float* depth, const uint8_t* labels, const float* T, const float* pose,
                      const float* rot, const uint8_t* not_done, int B, uint8_t* occ_out, uint8_t* sem_out,
                      void* stream) {
-    if (!T || !rot) return IVLN_E_INVALID;
+    if (!T || !rot || (m && m->open)) return IVLN_E_INVALID;
     return mapper_step(m, depth, labels, T, pose, rot, nullptr, nullptr, nullptr, not_done, B, occ_out, sem_out, stream);
 }
 
 int ivln_mapper_step_posed(ivln_mapper* m, const float* depth, const uint8_t* labels, const float* pose,
                            const double* orientation, const uint8_t* not_done, int B, uint8_t* occ_out,
                            uint8_t* sem_out, float* T_out, float* rot_out, void* stream) {
-    if (!orientation || !T_out || !rot_out) return IVLN_E_INVALID;
+    if (!orientation || !T_out || !rot_out || (m && m->open)) return IVLN_E_INVALID;
     return mapper_step(m, depth, labels, nullptr, pose, nullptr, orientation, T_out, rot_out, not_done, B, occ_out, sem_out,
                        stream);
 }
@@ -1487,6 +1515,7 @@ int ivln_mapper_env_counts(ivln_mapper* m, int B, int64_t* counts_host, void* st
 
 int ivln_mapper_env_export(ivln_mapper* m, int b, float* xyz, uint8_t* sem, int64_t max_n, int64_t* n_out, void* stream) {
     if (!m || !n_out || b < 0 || b >= m->B_max || max_n < 0 || (max_n > 0 && (!xyz || !sem))) return IVLN_E_INVALID;
+    if (m->open) return IVLN_E_INVALID;  // (the marks would share the table with an unfinished arg-max)
     if (m->known_rank != 0) return IVLN_E_UNSUPPORTED;
     EnvStat st[kBoxEnvs];
     int64_t total = 0;
@@ -1502,6 +1531,7 @@ int ivln_known_lib_add_from_mapper(ivln_known_lib* lib, int scene, ivln_mapper* 
     if (!lib || !m || scene < 0 || scene >= lib->max_scenes || lib->added[scene] || b < 0 || b >= m->B_max || max_n < 0)
         return IVLN_E_INVALID;
     if (max_n > 0 && (!records || ((uintptr_t)records & 15u))) return IVLN_E_INVALID;
+    if (m->open) return IVLN_E_INVALID;
     if (m->known_rank != 0) return IVLN_E_UNSUPPORTED;
     EnvStat st[kBoxEnvs];
     int64_t total = 0;
@@ -1522,6 +1552,7 @@ int ivln_known_lib_add_from_mapper(ivln_known_lib* lib, int scene, ivln_mapper* 
 
 // ---- seeding an iterative mapper (include/ivln_map_seed.h) ----
 static int seed_refused(const ivln_mapper* m) {
+    if (m->open) return IVLN_E_INVALID;  // (between an ivln_mapper_step_begin and its _finish the cloud is not to be touched)
     return (m->klib || m->known_rank != 0) ? IVLN_E_UNSUPPORTED : IVLN_OK;
 }
 
@@ -1578,5 +1609,30 @@ int ivln_mapper_env_append_from_lib(ivln_mapper* m, int b, const ivln_known_lib*
     const int rc = seed_refused(m);
     if (rc != IVLN_OK) return rc;
     return env_append(m, b, nullptr, nullptr, lib->table + scene, lib->count[scene], (hipStream_t)stream);
+}
+
+// ---- the table's invariant, observed (include/ivln_mapper_debug.h) ----
+int ivln_mapper_debug_nonzero(ivln_mapper* m, int64_t out[2], void* stream) {
+    if (!m || !out) return IVLN_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* d = nullptr;
+    unsigned long long h[2] = {0ull, 0ull};
+    HIPCHK(hipMalloc(&d, sizeof(h)));
+    const int64_t n[2] = {m->table_cells, (int64_t)m->B_max * m->rows * m->cols};
+    const unsigned long long* p[2] = {m->tab64, m->cell};
+    bool ok = hipMemsetAsync(d, 0, sizeof(h), s) == hipSuccess;
+    for (int k = 0; ok && k < 2; ++k) {
+        int64_t blocks = (n[k] + kThreads - 1) / kThreads;
+        if (blocks > kWorldBlocks) blocks = kWorldBlocks;
+        hipLaunchKernelGGL(k_debug_nonzero, dim3((unsigned)blocks), dim3(kThreads), 0, s, p[k], n[k], d + k);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    (void)hipFree(d);
+    if (!ok) return IVLN_E_HIP;
+    out[0] = (int64_t)h[0];
+    out[1] = (int64_t)h[1];
+    return IVLN_OK;
 }
 }  // extern "C"

@@ -331,7 +331,10 @@ class GraphedRollout:
                     dep, txt = run_A()
                     run_B2(0, dep, *run_B1(0, txt))
                 cap_stream.synchronize()
-            with torch.cuda.stream(self.sA):  # the side stream needs its own split-K workspace before capture
+            # the side stream needs its own split-K workspace before capture.  The mapper's half of run_A (the prefix's `begin`)
+            # has no per-stream state and no `finish` would follow it here: it stays out whatever warmup_mapper says - a
+            # dangling arg-max in the live mapper's table costs every later step the points it outranks
+            with self._dry_mapper(always=True), torch.cuda.stream(self.sA):
                 run_A()
         main.wait_stream(s)
         torch.cuda.synchronize()
@@ -442,17 +445,19 @@ class GraphedRollout:
         self.graphs[self.phase].replay()
 
     @contextlib.contextmanager
-    def _dry_mapper(self):
-        """Context: the transforms' mappers skip their own kernels (warmup_mapper=False), nothing otherwise."""
+    def _dry_mapper(self, always=False):
+        """Context: the transforms' mappers skip their own kernels (warmup_mapper=False, or `always`), nothing otherwise.
+        Nests: each mapper gets back the setting it had."""
         mods = (getattr(t, "mapping_module", None) for t in self.transforms)
-        mms = [] if self._warmup_mapper else [mm for mm in mods if mm is not None]
+        mms = [] if (self._warmup_mapper and not always) else [mm for mm in mods if mm is not None]
+        was = [getattr(mm, "dry_run", False) for mm in mms]
         for mm in mms:
             mm.dry_run = True
         try:
             yield
         finally:
-            for mm in mms:
-                mm.dry_run = False
+            for mm, w in zip(mms, was):
+                mm.dry_run = w
 
     def _capture(self, warmup):
         s = _stream(self.device, "warmup")

@@ -280,8 +280,15 @@ class MappingModule:
             pass
 
     def reset(self):
+        """Forgets the world cloud and an open `begin` with it (ivln_mapper_reset zeroes the arg-max table)."""
         if self._h is not None:
             check(lib().ivln_mapper_reset(self._h, stream_ptr()), "ivln_mapper_reset")
+        self._begin_open = False
+
+    def _refuse_open(self, what):
+        if self._begin_open:
+            raise _lib.IvlnError(f"MappingModule.{what}: `begin` is open - `finish` or `reset` it first (its arg-max entries "
+                                 "are in the mapper's table)")
 
     # -- frames -----------------------------------------------------------------------------
     def frames(self, pose: torch.Tensor, orientation: torch.Tensor):
@@ -325,6 +332,7 @@ class MappingModule:
         (obs_transforms.py:79-103): depth (B,H,W,1) f32, semantic12 (B,H,W,1) u8 (gt) or rgb
         (pred), world_robot_pose (B,3), world_robot_orientation (B,2) f64, not_done_masks (B,1),
         env_name list[str]."""
+        self._refuse_open("forward")
         depth = observations["depth"]
         B, H, W = depth.shape[0], depth.shape[1], depth.shape[2]
         if B > self.b_max:
@@ -409,6 +417,7 @@ class MappingModule:
         current stream).  Iterative mode with the posed entry only; `finish` must follow, ordered behind it."""
         if self.mode != "iterative" or not STEP_POSED:
             raise _lib.IvlnError("MappingModule.begin / finish: iterative mode with the posed step entry only")
+        self._refuse_open("begin")
         depth = observations["depth"]
         B, H, W = depth.shape[0], depth.shape[1], depth.shape[2]
         if B > self.b_max:
@@ -423,10 +432,10 @@ class MappingModule:
         orientation = observations["world_robot_orientation"].to(self.device, torch.float64).contiguous()
         # (finish reads pose / T / rot through the pointers begin was given: they stay alive on the module)
         self._open = (depth, not_done, pose, orientation)
-        self._begin_open = True
         check(lib().ivln_mapper_step_begin(self._h, dptr(depth), dptr(pose), dptr(orientation), dptr(not_done), B,
                                            dptr(self.map_memory._occ), dptr(self._T), dptr(self._rot), stream_ptr()),
               "ivln_mapper_step_begin")
+        self._begin_open = True  # (behind the call: a begin the handle refused has opened nothing)
 
     def finish(self, observations: Dict[str, torch.Tensor]) -> OccupancySemanticMapMemory:
         """Labels (gt, or the semantics module's) -> world-cloud merge -> maps (4 launches behind the labels)."""

@@ -451,11 +451,9 @@ class _Hip:
         order = np.argsort(rank[PAD:PAD + n].cpu().numpy(), kind="stable")
         return xyz[order], (meta[order] >> 8).astype(np.int32), (meta[order] & 0xFF).astype(np.uint8)
 
-    def step(self, s, entry="step"):
-        """one step through `entry` -> the bytes it left: occ, sem (B rows), T_out, rot_out (posed entries), the guard check"""
-        c, L, B = self.c, self.L, s["B"]
-        if s["width"] is not None:
-            self.set_width(s["width"])
+    def buffers(self, s):
+        """the step's inputs between their bands and B_max rows of sentinel-filled outputs (alive as long as the result is)"""
+        c = self.c
         cells = c.rows * c.cols
         keep = [_banded(s["depth"], float("nan")), _banded(s["labels"], 0xFF), _banded(s["pose"], float("nan")),
                 _banded(s["not_done"], 1), _banded(s["T"], float("nan")), _banded(s["rot"], float("nan")),
@@ -465,25 +463,49 @@ class _Hip:
         sem, psem = _out(c.B_max * cells, SENT_U8, torch.uint8)
         To, pT = _out(c.B_max * 16, SENT_F, torch.float32)
         ro, pr = _out(c.B_max * 9, SENT_F, torch.float32)
+        return types.SimpleNamespace(keep=keep, B=s["B"], dep=dep, lab=lab, pose=pose, nd=nd, T=T, rot=rot, ori=ori, occ=occ,
+                                     pocc=pocc, sem=sem, psem=psem, To=To, pT=pT, ro=ro, pr=pr)
+
+    def begin(self, q):
+        return self.L.ivln_mapper_step_begin(self.h, q.dep, q.pose, q.ori, q.nd, q.B, q.pocc, q.pT, q.pr, self.s)
+
+    def finish(self, q):
+        return self.L.ivln_mapper_step_finish(self.h, q.dep, q.lab, q.pT, q.pose, q.pr, q.nd, q.B, q.pocc, q.psem, self.s)
+
+    def call(self, q, entry):
+        """the return code of one step on the buffers q through `entry`"""
+        L, B = self.L, q.B
         if entry == "step":
-            rc = L.ivln_mapper_step(self.h, dep, lab, T, pose, rot, nd, B, pocc, psem, self.s)
-        elif entry == "frames":
-            rc = L.ivln_mapper_frames(pose, ori, B, pT, pr, self.s)
-            rc = rc or L.ivln_mapper_step(self.h, dep, lab, pT, pose, pr, nd, B, pocc, psem, self.s)
-        elif entry == "posed":
-            rc = L.ivln_mapper_step_posed(self.h, dep, lab, pose, ori, nd, B, pocc, psem, pT, pr, self.s)
-        else:
-            rc = L.ivln_mapper_step_begin(self.h, dep, pose, ori, nd, B, pocc, pT, pr, self.s)
-            rc = rc or L.ivln_mapper_step_finish(self.h, dep, lab, pT, pose, pr, nd, B, pocc, psem, self.s)
-        assert rc == 0, f"{entry}: return code {rc}"
+            return L.ivln_mapper_step(self.h, q.dep, q.lab, q.T, q.pose, q.rot, q.nd, B, q.pocc, q.psem, self.s)
+        if entry == "frames":
+            rc = L.ivln_mapper_frames(q.pose, q.ori, B, q.pT, q.pr, self.s)
+            return rc or L.ivln_mapper_step(self.h, q.dep, q.lab, q.pT, q.pose, q.pr, q.nd, B, q.pocc, q.psem, self.s)
+        if entry == "posed":
+            return L.ivln_mapper_step_posed(self.h, q.dep, q.lab, q.pose, q.ori, q.nd, B, q.pocc, q.psem, q.pT, q.pr, self.s)
+        return self.begin(q) or self.finish(q)
+
+    def result(self, q, entry, rows=None):
+        """the bytes a step left in q: occ, sem (B rows), T_out, rot_out (posed entries), the guard check.  rows: the rows
+        that may have been written (default B; 0: every output must be sentinels still)"""
+        c, B = self.c, q.B if rows is None else rows
+        cells = c.rows * c.cols
         torch.cuda.synchronize()
-        occ, sem, To, ro = occ.cpu().numpy(), sem.cpu().numpy(), To.cpu().numpy(), ro.cpu().numpy()
+        occ, sem, To, ro = q.occ.cpu().numpy(), q.sem.cpu().numpy(), q.To.cpu().numpy(), q.ro.cpu().numpy()
         guards = True
         for a, n, sent in [(occ, B * cells, SENT_U8), (sem, B * cells, SENT_U8),
                            (To, B * 16 if entry != "step" else 0, f32(SENT_F)), (ro, B * 9 if entry != "step" else 0, f32(SENT_F))]:
             guards &= bool((a[:PAD] == sent).all() and (a[PAD + n:] == sent).all())   # the bands and the rows >= B
         return dict(occ=occ[PAD:PAD + B * cells].reshape(B, c.rows, c.cols), sem=sem[PAD:PAD + B * cells].reshape(B, c.rows, c.cols),
                     T=To[PAD:PAD + B * 16].view(np.uint32), rot=ro[PAD:PAD + B * 9].view(np.uint32), guards=guards)
+
+    def step(self, s, entry="step"):
+        """one step through `entry` -> the bytes it left: occ, sem (B rows), T_out, rot_out (posed entries), the guard check"""
+        if s["width"] is not None:
+            self.set_width(s["width"])
+        q = self.buffers(s)
+        rc = self.call(q, entry)
+        assert rc == 0, f"{entry}: return code {rc}"
+        return self.result(q, entry)
 
 
 class _Cmp:

@@ -123,10 +123,13 @@ def test_act_matches_oracle_other_batches(B):
     assert float((lg.cpu() - lr).abs().max()) < 1e-4
 
 
-@pytest.mark.parametrize("streams,depth_mode", [(True, 0), (False, 2), ("split", 0), ("split", 2)])
-def test_graphed_multistream_rollout_is_bit_identical_to_eager(streams, depth_mode, same_depth_path):
+@pytest.mark.parametrize("streams,depth_mode,capture_with", [(True, 0, 0), (False, 2, 0), ("split", 0, 0), ("split", 2, 0), ("split", 0, 3)],
+                         ids=["True-0", "False-2", "split-0", "split-2", "split-0-other"])
+def test_graphed_multistream_rollout_is_bit_identical_to_eager(streams, depth_mode, capture_with, same_depth_path):
     """hipGraph replay (forked streams / one stream / three graphs on two streams) must not change a single
-    bit of actions / states / maps - with the depth encoder as the launch chain (0) and as the persistent launch (2)."""
+    bit of actions / states / maps - with the depth encoder as the launch chain (0) and as the persistent launch (2).
+    `other`: the capture's example batch is obs[3], not the first batch stepped - whatever the warm-up left in the mapper
+    has to be gone after its reset."""
     same_depth_path(depth_mode)
     from ivln_ce_amd.config import get_config
     from ivln_ce_amd.graphed import GraphedRollout
@@ -152,7 +155,7 @@ def test_graphed_multistream_rollout_is_bit_identical_to_eager(streams, depth_mo
         eager.append((a.clone(), rnn.clone(), b["occupancy_map"].clone(), b["semantic_map"].clone()))
     # graphed: the capture warm-up replays obs[0] a few times, so restart mapper + policy state afterwards
     tr_g = GTSemanticsIterativeMapper.from_config(cfg)
-    runner = GraphedRollout(pol, [tr_g], obs[0], deterministic=True, streams=streams)
+    runner = GraphedRollout(pol, [tr_g], obs[capture_with], deterministic=True, streams=streams)
     tr_g.mapping_module.reset()
     runner.reset_state()
     for t, o in enumerate(obs):
@@ -163,6 +166,18 @@ def test_graphed_multistream_rollout_is_bit_identical_to_eager(streams, depth_mo
         assert torch.equal(runner.rnn_states, eager[t][1]), f"rnn step {t}"
         assert torch.equal(mem.occupancy, eager[t][2]) and torch.equal(mem.semantic, eager[t][3]), f"maps step {t}"
     tr_g.mapping_module.check_status()
+    assert mapper_table_nonzero(tr_g.mapping_module) == [0, 0]
+
+
+def mapper_table_nonzero(mm):
+    """[non-zero slots of the arg-max table, non-zero raster words] of a MappingModule (include/ivln_mapper_debug.h)"""
+    import ctypes
+
+    from ivln_ce_amd._lib import lib, stream_ptr
+
+    out = (ctypes.c_int64 * 2)(-1, -1)
+    assert lib().ivln_mapper_debug_nonzero(mm._h, out, stream_ptr()) == 0
+    return [int(out[0]), int(out[1])]
 
 
 @pytest.mark.parametrize("streams", [True, False, "split"])

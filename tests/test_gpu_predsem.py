@@ -50,10 +50,10 @@ def _policy():
     return make_policy()
 
 
-def _obs(steps, seed):
+def _obs(steps, seed, n=B):
     from ivln_ce_amd.synthetic import SyntheticRollout
 
-    roll = SyntheticRollout(B=B, seed=seed, with_rgb=True)
+    roll = SyntheticRollout(B=n, seed=seed, with_rgb=True)
     cpu = [roll.step() for _ in range(steps)]
     dev = [{k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in o.items()} for o in cpu]
     return cpu, dev
@@ -112,22 +112,34 @@ def test_predsem_plugin_B8_rednet_mapper_policy_match_oracle():
         rnn_r, prev_r = sr, act.cpu()
 
 
-@pytest.mark.parametrize("streams", ["split", False])
-def test_predsem_graph_replay_is_bit_identical_to_eager_B8(streams, same_depth_path):
+@pytest.mark.parametrize("streams,capture_with,nb", [("split", 0, B), (False, 0, B), ("split", 3, 2), (False, 3, 2)],
+                         ids=["split", "False", "split-other", "False-other"])
+def test_predsem_graph_replay_is_bit_identical_to_eager_B8(streams, capture_with, nb, same_depth_path):
+    """`other` (2 envs): the capture's example batch is dev[3], the first batch stepped is dev[0].  With predicted semantics
+    the split capture records the mapper's label-free half at the head of the side graph - the only path where that prefix
+    is live: nothing the capture or its warm-up did with dev[3] may be left in the mapper behind its reset."""
+    from test_gpu_policy import mapper_table_nonzero
+
     from ivln_ce_amd.graphed import GraphedRollout
 
     same_depth_path(0)  # (the single-stream capture would otherwise take the persistent depth encoder, the eager pass the pairs)
     cfg = _cfg()
-    _, dev = _obs(5, seed=78)
+    _, dev = _obs(5, seed=78, n=nb)
     pol = _policy()
     # The runner fixes the depth encoder's launch strategy for its transformers (with predicted semantics RedNet is the
     # critical path and the encoder runs its conv + GroupNorm pairs, graphed.py) - build it first so that the eager
     # pass below runs the same kernels; "bit-identical" is a statement about launch order, not about two strategies.
     tr_g = _plugin(cfg, dev[0])
-    runner = GraphedRollout(pol, [tr_g], dev[0], deterministic=True, streams=streams)
+    runner = GraphedRollout(pol, [tr_g], dev[capture_with], deterministic=True, streams=streams)
+    # (the prefix is live in the split capture unless a switch takes it out: tests/test_gpu_switches.py runs this test with both)
+    off = os.environ.get("IVLN_MAPPER_PREFIX", "1") == "0" or os.environ.get("IVLN_PRED_DEPTH_START", "layer3") in ("0", "", "none")
+    assert runner._prefix == (streams == "split" and not off)
+    # the capture itself (default warmup_mapper=True) leaves nothing in the live mapper's table: its warm-ups are complete
+    # steps, the side stream's own warm-up runs the mapper dry, and a capture executes nothing - seen BEFORE the reset
+    assert mapper_table_nonzero(tr_g.mapping_module) == [0, 0] and not tr_g.mapping_module._begin_open
     tr_e = _plugin(cfg, dev[0])
-    rnn = torch.zeros(B, 2, 512, device=DEV)
-    prev = torch.zeros(B, 1, dtype=torch.long, device=DEV)
+    rnn = torch.zeros(nb, 2, 512, device=DEV)
+    prev = torch.zeros(nb, 1, dtype=torch.long, device=DEV)
     eager = []
     for o in dev:
         b = tr_e(dict(o))
@@ -136,6 +148,7 @@ def test_predsem_graph_replay_is_bit_identical_to_eager_B8(streams, same_depth_p
         prev = a
         eager.append((a.clone(), rnn.clone(), b["occupancy_map"].clone(), b["semantic_map"].clone()))
     tr_g.mapping_module.reset()
+    assert mapper_table_nonzero(tr_g.mapping_module) == [0, 0]
     runner.reset_state()
     for t, o in enumerate(dev):
         a = runner.step(o)
@@ -144,4 +157,33 @@ def test_predsem_graph_replay_is_bit_identical_to_eager_B8(streams, same_depth_p
         assert torch.equal(a, eager[t][0]), f"actions step {t}"
         assert torch.equal(runner.rnn_states, eager[t][1]), f"rnn step {t}"
         assert torch.equal(mem.occupancy, eager[t][2]) and torch.equal(mem.semantic, eager[t][3]), f"maps step {t}"
+        assert mapper_table_nonzero(tr_g.mapping_module) == [0, 0], f"table step {t}"
     tr_g.mapping_module.check_status()
+
+
+def test_first_capture_through_the_trainer_leaves_the_mappers_table_zero(same_depth_path):
+    """trainers._make_runner(first=True) with predicted semantics, the default warmup_mapper=True, 2 envs: the split capture's
+    warm-ups step the live mapper and the capture records the mapper's prefix; behind the runner's reset the arg-max table
+    holds nothing of all that (ivln_mapper_debug_nonzero), the cloud is empty and no `begin` is open."""
+    from test_gpu_policy import mapper_table_nonzero
+
+    from ivln_ce_amd import trainers
+
+    same_depth_path(0)
+    cfg = _cfg()
+    _, dev = _obs(2, seed=79, n=2)
+    tr = trainers.BaseVLNCETrainer.__new__(trainers.BaseVLNCETrainer)
+    tr.config, tr.device, tr.policy = cfg, DEV, _policy()
+    tr.rank, tr.local_rank, tr.world = 0, 0, 1
+    plugin = _plugin(cfg, dev[0])
+    tr.obs_transforms = [plugin]
+    rnn = torch.zeros(2, 2, 512, device=DEV)
+    prev = torch.zeros(2, 1, dtype=torch.long, device=DEV)
+    runner = tr._make_runner(dev[1], rnn, prev, first=True)
+    mm = plugin.mapping_module
+    assert runner._prefix and runner._warmup_mapper
+    assert mapper_table_nonzero(mm) == [0, 0]
+    assert mm.check_status() == 0 and not mm._begin_open and not getattr(mm, "dry_run", False)
+    runner.step(dev[0])   # another batch than the capture's, on the clean table
+    torch.cuda.synchronize()
+    assert mapper_table_nonzero(mm) == [0, 0] and mm.check_status() > 0
